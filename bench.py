@@ -15,10 +15,18 @@ path; per-GPU work is fixed as N grows ("weak").
 
 The JSON line also carries
   roofline     achieved algorithmic GB/s of the kernel (5 B/pixel: 1 read + 4 written) from HIP
-               events on the launch stream over the timed region, against the 8 TB/s HBM3E peak;
+               events on the launch stream over the timed region, against the 8 TB/s HBM3E peak.
+A plain run does only that: set-up (incl. the measured plan selection), pre-warm, W warm-up steps, the K
+timed steps, the optional --dump-outputs, the line.  --full adds everything else, after the timed region:
+  parity       a spot check of the batch against the CPU oracle (config.parity, per_gpu[].parity);
+  host_path    the PCIe-inclusive host path, three arms (rank 0, N == 1 only);
+  roofline.traffic  HBM bytes per launch measured by a rocprofv3 PMC child of this script (N == 1 only);
   cpu_baseline the CPU oracle (a port of the reference algorithm, oracle/) timed on this box's host
                cores on a bounded sample of the same frames (rank 0, N == 1 only).
 The oracle is imported here ONLY for that baseline leg and the parity spot check.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's BGRx batch) as float32 .npy files:
+a fixed, seeded sample of the batch and the border rows / columns of every frame (dump_outputs()).
 """
 import argparse
 import json
@@ -277,6 +285,38 @@ def parity_spot_check(pkg, ctxs, d_src, d_dst, rank, world, stream):
             raise AssertionError("bench parity check failed: rank %d local frame %d differs from "
                                  "the oracle in %d bytes" % (rank, local, int((got != want).sum())))
     return "bit-exact vs oracle on frames %d and %d of the batch (rggb->%s)" % (0, BATCH - 1, FORMAT)
+
+
+DUMP_SEED = 20261016             # fixes the sampled byte positions of --dump-outputs
+DUMP_SAMPLE = 6 << 20            # sampled bytes of the batch (float32: 24 MiB)
+DUMP_BORDER_ROWS = 2             # rows at the top and at the bottom of every frame
+DUMP_BORDER_COLS = 2             # pixels at the left and at the right edge of every row
+
+
+def dump_sample_index(total_bytes, n=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Sorted, distinct byte offsets into the output batch: the same for every run of the same geometry."""
+    import numpy as np
+    return np.unique(np.random.default_rng(seed).integers(0, total_bytes, n, dtype=np.int64))
+
+
+def dump_outputs(out_dir, d_dst, frames, height, row_bytes):
+    """The BGRx batch the last timed step wrote (d_dst: uint8 device tensor, frames x height x row_bytes), as float32
+    arrays in out_dir: bgrx_sample.npy (the bytes at dump_sample_index(), in index order) and bgrx_border_rows.npy /
+    bgrx_border_cols.npy (frames x rows x row_bytes, frames x height x bytes: the demosaic's edge cases).  The whole
+    batch is 2 GB; these are about 50 MB."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = torch.from_numpy(dump_sample_index(d_dst.numel())).to(d_dst.device)
+    batch = d_dst.view(frames, height, row_bytes)
+    rows = list(range(DUMP_BORDER_ROWS)) + list(range(height - DUMP_BORDER_ROWS, height))
+    cols = list(range(4 * DUMP_BORDER_COLS)) + list(range(row_bytes - 4 * DUMP_BORDER_COLS, row_bytes))
+    arrays = {"bgrx_sample": d_dst[idx],
+              "bgrx_border_rows": batch[:, rows, :],
+              "bgrx_border_cols": batch[:, :, cols]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(torch.float32).cpu().numpy())
+    return sorted(arrays)
 
 
 def sched_snapshot():
@@ -975,6 +1015,9 @@ def run(args):
 
     tinfo = {}
     elapsed = timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, dist, tinfo)
+    if args.dump_outputs and rank == 0:
+        # before anything else launches on d_dst: it holds what the last timed step wrote
+        dump_outputs(args.dump_outputs, d_dst, BATCH, HEIGHT, ctx0.dst_bytes // HEIGHT)
     if step_events is not None:
         kernel_ms = step_events[0].elapsed_time(step_events[args.steps]) / args.steps
         per_step = sorted(step_events[k].elapsed_time(step_events[k + 1]) for k in range(args.steps))
@@ -988,7 +1031,7 @@ def run(args):
     kernel_ms_max = dist.max_over_ranks(kernel_ms) if dist is not None else kernel_ms
     barrier_ms = dist.max_over_ranks(tinfo.get("barrier_ms", 0.0)) if dist is not None else 0.0
     # parity AFTER the timed region (host-side oracle work and 33 MB downloads would idle the GPU before it)
-    parity = parity_spot_check(pkg, ctxs, d_src, d_dst, rank, world, stream)
+    parity = parity_spot_check(pkg, ctxs, d_src, d_dst, rank, world, stream) if args.full else None
 
     def pct(q):
         return per_step[min(len(per_step) - 1, int(q * len(per_step)))]
@@ -1042,11 +1085,11 @@ def run(args):
     # in host scheduling: no thread of this process waited for a CPU meanwhile) -- that, inside a 15-ms arm right behind
     # the child, was the "5.7 Gpix/s" of the default host mode in two records of rounds 4-5.  --host-path-after-traffic
     # restores the old order (the reproducer).
-    if rank == 0 and world == 1 and not args.no_host_path and not args.host_path_after_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_host_path and not args.host_path_after_traffic:
         for c in ctxs.values():
             c.sync()
         result["host_path"] = host_path_note(pkg, local_rank)
-    if rank == 0 and world == 1 and not args.no_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic:
         # measured in THIS run: a profiled child of this very script, same batch, same plan, after the timed region
         torch.cuda.synchronize()
         vid, band, align = ctx0.get_plan()
@@ -1066,7 +1109,7 @@ def run(args):
                     kernel_variant=ctx0.variant_name, band=ctx0.launch_geometry(BATCH)["band"],
                     plan_source=PLAN_SOURCES[ctx0.get_plan_for(BATCH)[3]], parity=parity)
         result["per_gpu"] = dist.gather_objects(mine)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_host_path and args.host_path_after_traffic:
             for c in ctxs.values():
                 c.sync()
@@ -1088,6 +1131,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--variant", type=int, default=int(os.environ.get("MIBAYER_VARIANT", "0")))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the parity spot check, the host-path note, the in-run PMC "
+                         "traffic pass and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as float32 .npy files into DIR")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-host-path", action="store_true")
@@ -1117,6 +1165,8 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing only: ranks share the visible GPUs (use with --backend gloo on a 1-GPU box)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "batch":
+        ap.error("--dump-outputs dumps the batch of the device-resident mode (--mode batch)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # convenience: self-launch one rank per GPU the way the driver does
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",

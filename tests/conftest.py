@@ -79,3 +79,12 @@ def golden_r2b():
     """rgb2bayer fixtures: outputs of the reference's own gst_rgb2bayer_transform (tests/golden/make_golden.py)."""
     import numpy as np
     return np.load(os.path.join(ROOT, "tests", "golden", "rgb2bayer_small.npz"))
+
+
+@pytest.fixture(scope="session")
+def reference_pins():
+    """md5s of what the reference's own compiled functions (oracle/_ref) return for the inputs of the tests that pin
+    against them, recorded by tests/golden/make_reference_pins.py: those tests run without oracle/_ref too."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_pins.json")) as f:
+        return json.load(f)["cases"]

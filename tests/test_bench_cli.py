@@ -131,3 +131,39 @@ def test_cpu_baseline_has_the_simd_leg_and_uses_every_core(monkeypatch):
     assert cb["all_cores"]["jobs"] >= min(2 * ncores, 4 * 64)       # at least two jobs per core (bounded by the rows)
     if cb["reference_c_path"] is not None:
         assert cb["reference_c_path"]["kind"] == "reference" and cb["reference_c_path"]["cores"] == 1
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: the sampled byte positions are the same in every run (two builds are compared output for
+    output), distinct, in range and sorted; the three arrays of the bench batch stay within 64 MB as float32."""
+    import numpy as np
+    total = bench.BATCH * bench.HEIGHT * 4 * bench.WIDTH
+    a, b = bench.dump_sample_index(total), bench.dump_sample_index(total)
+    assert np.array_equal(a, b) and a[0] >= 0 and a[-1] < total and (np.diff(a) > 0).all()
+    assert len(a) > 0.99 * bench.DUMP_SAMPLE
+    rows = bench.BATCH * 2 * bench.DUMP_BORDER_ROWS * 4 * bench.WIDTH
+    cols = bench.BATCH * bench.HEIGHT * 2 * 4 * bench.DUMP_BORDER_COLS
+    assert 4 * (len(a) + rows + cols) <= 64e6
+
+
+def test_dump_outputs_writes_float32_copies_of_the_batch(tmp_path):
+    """dump_outputs() on a host tensor: every array is float32 and holds exactly the bytes of the batch it names."""
+    import numpy as np
+    import torch
+    frames, height, row_bytes = 3, 7, 48
+    batch = np.random.default_rng(1).integers(0, 256, (frames, height, row_bytes), dtype=np.uint8)
+    names = bench.dump_outputs(str(tmp_path), torch.from_numpy(batch.reshape(-1).copy()), frames, height, row_bytes)
+    assert names == ["bgrx_border_cols", "bgrx_border_rows", "bgrx_sample"]
+    got = {n: np.load(str(tmp_path / (n + ".npy"))) for n in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["bgrx_sample"], batch.reshape(-1)[bench.dump_sample_index(batch.size)])
+    rows = [0, 1, height - 2, height - 1]
+    cols = list(range(8)) + list(range(row_bytes - 8, row_bytes))
+    assert np.array_equal(got["bgrx_border_rows"], batch[:, rows, :])
+    assert np.array_equal(got["bgrx_border_cols"], batch[:, :, cols])
+
+
+def test_dump_outputs_is_refused_in_stream_mode(tmp_path):
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "stream", "--dump-outputs",
+                          str(tmp_path)], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--dump-outputs" in res.stderr and "{" not in res.stdout

@@ -46,7 +46,7 @@ def test_force_dist_brings_rccl_up_on_one_rank(gpu_pkg):
     """the process-group set-up of the N > 1 flow -- gloo bootstrap, an RCCL group, the probe
     all-reduce, both barriers of the timed region and the MAX reduce on a device tensor -- executed on real hardware
     by one rank, so the driver's SCALE run is not the first process that ever takes the RCCL branch."""
-    common = ["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu", "--no-host-path", "--no-traffic"]
+    common = ["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu", "--no-host-path", "--no-traffic"]
     plain, _ = run_bench(common)
     dist, err = run_bench(common + ["--force-dist"])
     assert dist["control_plane"] == "nccl" and dist["control_plane_fallback"] is None, err[-2000:]
@@ -74,7 +74,7 @@ def test_traffic_is_measured_inside_the_bench_run(gpu_pkg):
     rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE after the timed region), for the very plan the timed region ran."""
     if bench.find_rocprofv3() is None:
         pytest.fail("rocprofv3 is not installed on the GPU box")
-    j, err = run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu", "--no-host-path"])
+    j, err = run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu", "--no-host-path"])
     t = j["roofline"]["traffic"]
     assert t is not None, j["roofline"].get("traffic_note")
     assert 0.99 <= t["ratio"] <= 1.30 and 0.99 <= t["write_ratio"] <= 1.02 and 0.99 <= t["read_ratio"] <= 2.1, t
@@ -97,7 +97,7 @@ def test_perf_floor_of_the_drivers_command(gpu_pkg):
     that costs 3 points turns this red instead of waiting for a judge."""
     best = None
     for attempt in range(2):            # a box that is still clocking up gets one more chance; a regression fails both
-        j, err = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu", "--no-host-path"])
+        j, err = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-host-path"])
         if best is None or j["roofline"]["frac"] > best["roofline"]["frac"]:
             best = j
         if best["roofline"]["frac"] >= 0.78:
@@ -113,6 +113,40 @@ def test_perf_floor_of_the_drivers_command(gpu_pkg):
     assert "traffic_profiled" not in r                       # one record, one traffic figure
     assert best["metric"].startswith("bayer2rgb Mpix/s @4K") and best["dtype"] == "u8" and best["n_gpus"] == 1
     assert best["config"]["plan_source"] == "measured"
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(gpu_pkg, oracle, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and leaves out the parity check, the host path, the PMC
+    child and the CPU baseline; --dump-outputs writes what the last timed step computed: the border rows and columns
+    of the first and the last frame of the batch, and the sampled bytes inside them, equal the oracle's."""
+    import numpy as np
+    steps, warmup = 7, 3
+    j, err = run_bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path)])
+    assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0
+    assert abs(j["value"] - 3840 * 2160 * 64 / (j["ms_per_step"] * 1e-3) / 1e6) / j["value"] < 0.01
+    assert not {"cpu_baseline", "host_path"} & set(j) and j["roofline"]["traffic"] is None
+    assert j["config"]["parity"] is None
+    W, H, N = bench.WIDTH, bench.HEIGHT, bench.BATCH
+    rows = np.load(str(tmp_path / "bgrx_border_rows.npy"))
+    cols = np.load(str(tmp_path / "bgrx_border_cols.npy"))
+    sample = np.load(str(tmp_path / "bgrx_sample.npy"))
+    assert rows.dtype == cols.dtype == sample.dtype == np.float32
+    assert rows.shape == (N, 4, 4 * W) and cols.shape == (N, H, 16)
+    idx = bench.dump_sample_index(N * H * 4 * W)
+    assert sample.shape == idx.shape
+    order = bench.ORDERS[(warmup + steps - 1) % 4]          # the order of the last timed step
+    r, g, b = oracle.LAYOUTS[bench.FORMAT]
+    frame_bytes = H * 4 * W
+    for f in (0, N - 1):
+        src = oracle.fill_synthetic(W, H, 1, bench.SEED, first_frame=f)[0]
+        want = oracle.bayer2rgb(src, W, order, r, g, b)
+        assert np.array_equal(rows[f], want[[0, 1, H - 2, H - 1]]), f
+        assert np.array_equal(cols[f], want[:, list(range(8)) + list(range(4 * W - 8, 4 * W))]), f
+        mine = (idx >= f * frame_bytes) & (idx < (f + 1) * frame_bytes)
+        assert mine.sum() > 1000
+        assert np.array_equal(sample[mine], want.reshape(-1)[idx[mine] - f * frame_bytes]), f
 
 
 @pytest.mark.gpu

@@ -170,25 +170,42 @@ def test_known_md5_answers_full_size(gpu_pkg):
             ctx.device_free(d_dst)
 
 
-def test_hip_equals_the_reference_frame_driver_directly(gpu_pkg, oracle):
-    """HIP output against the REFERENCE'S OWN gst_bayer2rgb_process (gstbayer2rgb.c:387-451, compiled into
-    oracle/_ref/libbayer_frame_ref.so, which travels to the GPU box as a binary) with no restatement in between:
-    1080p, 4K, camera geometries off every grid, one order x layout each way round."""
-    if not oracle.have_ref_frame():
-        pytest.skip("oracle/_ref/libbayer_frame_ref.so not on this box")
+HIP_FRAME_DRIVER_CASES = [
+    (1920, 1080, "rggb", "BGRx"), (3840, 2160, "bggr", "RGBx"), (3840, 2160, "grbg", "xBGR"), (3838, 2160, "gbrg", "ARGB"),
+    (4056, 3040, "rggb", "RGBA"), (1366, 768, "grbg", "BGRA"), (2590, 1942, "bggr", "xRGB"), (640, 480, "bggr", "RGBx"),
+    (4, 3, "gbrg", "ABGR"), (66, 7, "rggb", "BGRx")]
+
+
+def hip_frame_driver_cases():
+    """The inputs of test_hip_equals_the_reference_frame_driver_directly, in the order they are drawn."""
     rng = np.random.default_rng(77)
-    cases = [(1920, 1080, "rggb", "BGRx"), (3840, 2160, "bggr", "RGBx"), (3840, 2160, "grbg", "xBGR"),
-             (3838, 2160, "gbrg", "ARGB"), (4056, 3040, "rggb", "RGBA"), (1366, 768, "grbg", "BGRA"),
-             (2590, 1942, "bggr", "xRGB"), (640, 480, "bggr", "RGBx"), (4, 3, "gbrg", "ABGR"), (66, 7, "rggb", "BGRx")]
-    for (w, h, pat, fmt) in cases:
+    for (w, h, pat, fmt) in HIP_FRAME_DRIVER_CASES:
         src = rng.integers(0, 256, (h, (w + 3) & ~3), dtype=np.uint8)
+        yield dict(key="%dx%d/%s/%s" % (w, h, pat, fmt), src=src, w=w, pat=pat, fmt=fmt)
+
+
+def test_hip_equals_the_reference_frame_driver_directly(gpu_pkg, oracle, reference_pins):
+    """HIP output against the REFERENCE'S OWN gst_bayer2rgb_process (gstbayer2rgb.c:387-451) with no restatement in
+    between: 1080p, 4K, camera geometries off every grid, one order x layout each way round.  Against the md5 of the
+    reference's output recorded for the same input (tests/golden/reference_pins.json), and byte for byte against the
+    compiled function where oracle/_ref/libbayer_frame_ref.so was built and travelled with the tree."""
+    live = oracle.have_ref_frame()
+    pins = reference_pins["hip_frame_driver"]
+    n = 0
+    for c in hip_frame_driver_cases():
+        src, w, pat, fmt = c["src"], c["w"], c["pat"], c["fmt"]
+        h = src.shape[0]
         r, g, b = gpu_pkg.FORMATS[fmt]
-        want = oracle.ref_frame_bayer2rgb(src, w, pat, r, g, b)
+        assert md5(src) == pins[c["key"]]["in"], c["key"]
         with gpu_pkg.Context(w, h, pat, fmt, src_stride=src.shape[1]) as ctx:
             got_d = ctx.process_batch_via_device(src[None])[0]
             got_h = ctx.process_host(src)
-        assert np.array_equal(got_d, want), (w, h, pat, fmt)
-        assert np.array_equal(got_h, want), (w, h, pat, fmt)
+        assert md5(got_d) == pins[c["key"]]["out"], (w, h, pat, fmt)
+        assert np.array_equal(got_h, got_d), (w, h, pat, fmt)
+        if live:
+            assert np.array_equal(got_d, oracle.ref_frame_bayer2rgb(src, w, pat, r, g, b)), (w, h, pat, fmt)
+        n += 1
+    assert n == len(HIP_FRAME_DRIVER_CASES) == len(pins)
 
 
 def test_batch_launch_equals_per_frame(gpu_pkg, oracle):
@@ -1548,7 +1565,7 @@ def _bench_two_ranks(extra, port):
 def test_bench_two_ranks_batch_mode():
     """the N > 1 flow of bench.py -- process-group set-up, frame sharding g -> rank g % N, barriers,
     max-over-ranks, the per-GPU gather -- runs every round, not for the first time in a SCALE run."""
-    j = _bench_two_ranks(["--steps", "5", "--warmup", "2", "--no-cpu", "--no-host-path"], 29611)
+    j = _bench_two_ranks(["--steps", "5", "--warmup", "2", "--full", "--no-cpu", "--no-host-path"], 29611)
     assert j["n_gpus"] == 2 and j["steps"] == 5 and j["warmup"] == 2 and j["scaling"] == "weak"
     assert j["unit"] == "Mpix/s" and j["dtype"] == "u8" and j["higher_is_better"] is True
     assert len(j["per_gpu"]) == 2 and sorted(p["rank"] for p in j["per_gpu"]) == [0, 1]

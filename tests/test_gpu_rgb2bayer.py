@@ -59,19 +59,37 @@ def test_rgb2bayer_known_md5_answers_full_size(gpu_pkg):
         assert hashlib.md5(np.ascontiguousarray(got[:, :w]).tobytes()).hexdigest() == e["md5_output"], e
 
 
-def test_rgb2bayer_equals_the_reference_transform_directly(gpu_pkg, oracle):
-    """HIP mosaic against the REFERENCE'S OWN gst_rgb2bayer_transform (oracle/_ref/libbayer_frame_ref.so on this box),
-    no restatement in between: 4K, 1080p, odd and padded geometries."""
-    if not oracle.have_ref_frame():
-        pytest.skip("oracle/_ref/libbayer_frame_ref.so not on this box")
+HIP_R2B_TRANSFORM_CASES = [(3840, 2160, 0, "rggb"), (1920, 1080, 0, "gbrg"), (3841, 2161, 0, "grbg"),
+                           (1367, 769, 40, "bggr"), (5, 7, 8, "gbrg"), (1, 1, 0, "rggb")]
+
+
+def hip_rgb2bayer_transform_cases():
+    """The inputs of test_rgb2bayer_equals_the_reference_transform_directly, in the order they are drawn."""
     rng = np.random.default_rng(78)
-    for (w, h, pad, pat) in [(3840, 2160, 0, "rggb"), (1920, 1080, 0, "gbrg"), (3841, 2161, 0, "grbg"),
-                             (1367, 769, 40, "bggr"), (5, 7, 8, "gbrg"), (1, 1, 0, "rggb")]:
+    for (w, h, pad, pat) in HIP_R2B_TRANSFORM_CASES:
         src = rng.integers(0, 256, (h, 4 * w + pad), dtype=np.uint8)
-        want = oracle.ref_frame_rgb2bayer(src, w, pat)
-        with gpu_pkg.Context(w, h, pat, (1, 2, 3), src_stride=4 * w + pad, flags=gpu_pkg.FLAG_RGB2BAYER) as ctx:
-            got = ctx.process_batch_via_device(src[None])[0]
-        assert np.array_equal(got[:, :w], want[:, :w]), (w, h, pad, pat)
+        yield dict(key="%dx%dp%d/%s" % (w, h, pad, pat), src=src, w=w, pat=pat)
+
+
+def test_rgb2bayer_equals_the_reference_transform_directly(gpu_pkg, oracle, reference_pins):
+    """HIP mosaic against the REFERENCE'S OWN gst_rgb2bayer_transform, no restatement in between: 4K, 1080p, odd and
+    padded geometries.  Against the md5 of the reference's mosaic recorded for the same input
+    (tests/golden/reference_pins.json), and byte for byte against the compiled function where
+    oracle/_ref/libbayer_frame_ref.so was built and travelled with the tree."""
+    live = oracle.have_ref_frame()
+    pins = reference_pins["hip_rgb2bayer_transform"]
+    n = 0
+    for c in hip_rgb2bayer_transform_cases():
+        src, w, pat = c["src"], c["w"], c["pat"]
+        h, stride = src.shape
+        assert hashlib.md5(src.tobytes()).hexdigest() == pins[c["key"]]["in"], c["key"]
+        with gpu_pkg.Context(w, h, pat, (1, 2, 3), src_stride=stride, flags=gpu_pkg.FLAG_RGB2BAYER) as ctx:
+            got = np.ascontiguousarray(ctx.process_batch_via_device(src[None])[0][:, :w])
+        assert hashlib.md5(got.tobytes()).hexdigest() == pins[c["key"]]["out"], c["key"]
+        if live:
+            assert np.array_equal(got, oracle.ref_frame_rgb2bayer(src, w, pat)[:, :w]), c["key"]
+        n += 1
+    assert n == len(HIP_R2B_TRANSFORM_CASES) == len(pins)
 
 
 def test_rgb2bayer_matches_oracle_all_sizes(gpu_pkg, oracle):

@@ -87,66 +87,106 @@ def r2b_key_dims(name):
     return key, w, h, int(pad or 0)
 
 
-def test_oracle_equals_reference_frame_driver(oracle):
-    """The restated frame driver (ring priming, up(0) = 1, dn(H-1) = H-4, the four edge columns, pattern symmetry)
-    against the REFERENCE'S OWN gst_bayer2rgb_process (gstbayer2rgb.c:387-451) compiled here: golden size list,
-    camera widths off every grid, padded source and destination rows; C and NumPy forms."""
-    if not oracle.have_ref_frame():
-        pytest.skip("oracle/_ref/libbayer_frame_ref.so not built (needs /root/reference at build time)")
+FRAME_DRIVER_SIZES = [(w, h) for w in (4, 6, 8, 66) for h in (3, 4, 5, 6, 7)] + [
+    (64, 48), (16, 3), (258, 9), (130, 33), (1366, 11), (3838, 6), (4056, 5), (2590, 7), (640, 480), (1920, 31)]
+
+
+def frame_driver_cases(oracle):
+    """The inputs of test_oracle_equals_reference_frame_driver, in the order they are drawn: dicts of key (the case's
+    name in tests/golden/reference_pins.json), src, width, pattern, (r, g, b) and dst_stride."""
     rng = np.random.default_rng(55)
-    sizes = [(w, h) for w in (4, 6, 8, 66) for h in (3, 4, 5, 6, 7)] + [
-        (64, 48), (16, 3), (258, 9), (130, 33), (1366, 11), (3838, 6), (4056, 5), (2590, 7), (640, 480), (1920, 31)]
-    n = 0
-    for (w, h) in sizes:
+    for (w, h) in FRAME_DRIVER_SIZES:
         src = rng.integers(0, 256, (h, (w + 3) & ~3), dtype=np.uint8)
         if w == 66:
             src[::2] = 255
             src[1::2] &= 1
         for pat in PATTERNS:
             for lay in sorted(oracle.LAYOUTS):
-                r, g, b = oracle.LAYOUTS[lay]
-                want = oracle.ref_frame_bayer2rgb(src, w, pat, r, g, b)
-                assert np.array_equal(oracle.bayer2rgb(src, w, pat, r, g, b), want), (w, h, pat, lay)
-                if w * h <= 70 * 70:
-                    got_np = oracle.np_oracle.bayer2rgb(src[:, :w], pat, r, g, b).reshape(h, 4 * w)
-                    assert np.array_equal(got_np, want), (w, h, pat, lay)
-                n += 1
-    assert n == len(sizes) * 4 * len(oracle.LAYOUTS)
+                yield dict(key="%dx%d/%s/%s" % (w, h, pat, lay), src=src, w=w, pat=pat, rgb=oracle.LAYOUTS[lay],
+                           dst_stride=None)
     # padded rows on both sides: the reference honours the strides it is given (:476-477)
     src = rng.integers(0, 256, (9, 140), dtype=np.uint8)
-    a = oracle.ref_frame_bayer2rgb(src, 130, "gbrg", 3, 2, 1, dst_stride=4 * 130 + 40)
-    assert np.array_equal(a, oracle.bayer2rgb(src, 130, "gbrg", 3, 2, 1, dst_stride=4 * 130 + 40))
-    assert (a[:, 4 * 130:] == 0xA5).all()
+    yield dict(key="130x9/gbrg/321/pad", src=src, w=130, pat="gbrg", rgb=(3, 2, 1), dst_stride=4 * 130 + 40)
 
 
-def test_known_md5_answers_reproduce_through_the_reference_frame_driver(oracle):
-    if not oracle.have_ref_frame():
-        pytest.skip("oracle/_ref/libbayer_frame_ref.so not built")
+def test_oracle_equals_reference_frame_driver(oracle, reference_pins):
+    """The restated frame driver (ring priming, up(0) = 1, dn(H-1) = H-4, the four edge columns, pattern symmetry)
+    against the REFERENCE'S OWN gst_bayer2rgb_process (gstbayer2rgb.c:387-451): golden size list, camera widths off
+    every grid, padded source and destination rows; C and NumPy forms.  Byte for byte against the compiled function
+    where oracle/_ref was built, and always against the md5 of its output recorded for the same input
+    (tests/golden/reference_pins.json)."""
+    live = oracle.have_ref_frame()
+    pins = reference_pins["frame_driver"]
+    n = 0
+    for c in frame_driver_cases(oracle):
+        src, w, pat, (r, g, b), ds = c["src"], c["w"], c["pat"], c["rgb"], c["dst_stride"]
+        h = src.shape[0]
+        got = oracle.bayer2rgb(src, w, pat, r, g, b, dst_stride=ds)
+        assert md5(src) == pins[c["key"]]["in"], c["key"]
+        assert md5(got) == pins[c["key"]]["out"], c["key"]
+        if live:
+            assert np.array_equal(got, oracle.ref_frame_bayer2rgb(src, w, pat, r, g, b, dst_stride=ds)), c["key"]
+        if ds is None and w * h <= 70 * 70:
+            got_np = oracle.np_oracle.bayer2rgb(src[:, :w], pat, r, g, b).reshape(h, 4 * w)
+            assert np.array_equal(got_np, got), c["key"]
+        if ds is not None:
+            assert (got[:, 4 * w:] == 0xA5).all()
+        n += 1
+    assert n == len(FRAME_DRIVER_SIZES) * 4 * len(oracle.LAYOUTS) + 1 == len(pins)
+
+
+def test_known_md5_answers_reproduce_through_the_reference_frame_driver(oracle, reference_pins):
+    """The whole-element known answers are what the reference's frame driver gives: run where
+    oracle/_ref was built, and as recorded for the same inputs (tests/golden/reference_pins.json) everywhere."""
     with open(os.path.join(ROOT, "tests", "golden", "known_md5.json")) as f:
         entries = json.load(f)["entries"]
+    pins = reference_pins["known_md5"]
+    n = 0
     for e in entries:
         if e["width"] > 3840:
             continue        # 8K: covered by make_golden.py itself; keep the CPU suite short
-        src = oracle.fill_synthetic(e["width"], e["height"], 1, e["seed"])[0]
-        r, g, b = oracle.LAYOUTS[e["format"]]
-        assert md5(oracle.ref_frame_bayer2rgb(src, e["width"], e["pattern"], r, g, b)) == e["md5_output"], e
+        key = "%dx%d/%d/%s/%s" % (e["width"], e["height"], e["seed"], e["pattern"], e["format"])
+        assert pins[key]["in"] == e["md5_input"] and pins[key]["out"] == e["md5_output"], e
+        n += 1
+        if oracle.have_ref_frame():
+            src = oracle.fill_synthetic(e["width"], e["height"], 1, e["seed"])[0]
+            r, g, b = oracle.LAYOUTS[e["format"]]
+            assert md5(oracle.ref_frame_bayer2rgb(src, e["width"], e["pattern"], r, g, b)) == e["md5_output"], e
+    assert n == len(pins) >= 6
 
 
-def test_rgb2bayer_oracle_equals_reference_transform(oracle):
-    """oracle.rgb2bayer (C and NumPy) against the REFERENCE'S OWN gst_rgb2bayer_transform (gstrgb2bayer.c:229-278)
-    compiled here: odd and even sizes, padded source rows (GstVideoMeta stride), all four orders."""
-    if not oracle.have_ref_frame():
-        pytest.skip("oracle/_ref/libbayer_frame_ref.so not built (needs /root/reference at build time)")
+R2B_TRANSFORM_SIZES = [(1, 1, 0), (2, 3, 0), (3, 2, 0), (5, 7, 0), (5, 7, 8), (16, 9, 0), (66, 50, 0), (101, 33, 0),
+                       (130, 21, 24), (257, 5, 0), (1030, 17, 0), (1920, 31, 0), (3840, 9, 0)]
+
+
+def rgb2bayer_transform_cases():
+    """The inputs of test_rgb2bayer_oracle_equals_reference_transform, in the order they are drawn."""
     rng = np.random.default_rng(56)
-    for (w, h, pad) in [(1, 1, 0), (2, 3, 0), (3, 2, 0), (5, 7, 0), (5, 7, 8), (16, 9, 0), (66, 50, 0), (101, 33, 0),
-                        (130, 21, 24), (257, 5, 0), (1030, 17, 0), (1920, 31, 0), (3840, 9, 0)]:
+    for (w, h, pad) in R2B_TRANSFORM_SIZES:
         src = rng.integers(0, 256, (h, 4 * w + pad), dtype=np.uint8)
         for pat in PATTERNS:
-            want = oracle.ref_frame_rgb2bayer(src, w, pat)
-            got = oracle.rgb2bayer(src, w, pat, 1, 2, 3)
-            assert np.array_equal(got, want), (w, h, pad, pat)      # incl. the untouched padding columns
-            got_np = oracle.np_oracle.rgb2bayer(src[:, :4 * w].reshape(h, w, 4), pat, 1, 2, 3)
-            assert np.array_equal(got_np, want[:, :w]), (w, h, pad, pat)
+            yield dict(key="%dx%dp%d/%s" % (w, h, pad, pat), src=src, w=w, pat=pat)
+
+
+def test_rgb2bayer_oracle_equals_reference_transform(oracle, reference_pins):
+    """oracle.rgb2bayer (C and NumPy) against the REFERENCE'S OWN gst_rgb2bayer_transform (gstrgb2bayer.c:229-278):
+    odd and even sizes, padded source rows (GstVideoMeta stride), all four orders.  Byte for byte against the compiled
+    function where oracle/_ref was built, and always against the md5 of its output recorded for the same input."""
+    live = oracle.have_ref_frame()
+    pins = reference_pins["rgb2bayer_transform"]
+    n = 0
+    for c in rgb2bayer_transform_cases():
+        src, w, pat = c["src"], c["w"], c["pat"]
+        h = src.shape[0]
+        got = oracle.rgb2bayer(src, w, pat, 1, 2, 3)
+        assert md5(src) == pins[c["key"]]["in"], c["key"]
+        assert md5(got) == pins[c["key"]]["out"], c["key"]               # incl. the untouched padding columns
+        if live:
+            assert np.array_equal(got, oracle.ref_frame_rgb2bayer(src, w, pat)), c["key"]
+        got_np = oracle.np_oracle.rgb2bayer(src[:, :4 * w].reshape(h, w, 4), pat, 1, 2, 3)
+        assert np.array_equal(got_np, got[:, :w]), c["key"]
+        n += 1
+    assert n == len(R2B_TRANSFORM_SIZES) * 4 == len(pins)
 
 
 def test_rgb2bayer_golden_fixtures_and_known_md5(oracle, golden_r2b):
@@ -171,19 +211,35 @@ def test_rgb2bayer_golden_fixtures_and_known_md5(oracle, golden_r2b):
         assert md5(oracle.rgb2bayer(src, w, e["pattern"], 1, 2, 3)[:, :w]) == e["md5_output"], e
 
 
-def test_own_rows_equal_reference_rows(oracle):
-    if not oracle.have_ref_rows():
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+REF_ROWS_SIZES = [(4, 3), (6, 4), (66, 50), (64, 48), (130, 33), (1920, 8)]
+
+
+def ref_rows_cases(oracle):
+    """The inputs of test_own_rows_equal_reference_rows, in the order they are drawn."""
     rng = np.random.default_rng(5)
-    for (w, h) in [(4, 3), (6, 4), (66, 50), (64, 48), (130, 33), (1920, 8)]:
-        stride = (w + 3) & ~3
-        src = rng.integers(0, 256, (h, stride), dtype=np.uint8)
+    for (w, h) in REF_ROWS_SIZES:
+        src = rng.integers(0, 256, (h, (w + 3) & ~3), dtype=np.uint8)
         for pat in PATTERNS:
             for lay in LAYOUTS:
-                r, g, b = oracle.LAYOUTS[lay]
-                a = oracle.bayer2rgb(src, w, pat, r, g, b)
-                b_ = oracle.bayer2rgb(src, w, pat, r, g, b, ref_rows=True)
-                assert np.array_equal(a, b_), (w, h, pat, lay)
+                yield dict(key="%dx%d/%s/%s" % (w, h, pat, lay), src=src, w=w, pat=pat, rgb=oracle.LAYOUTS[lay])
+
+
+def test_own_rows_equal_reference_rows(oracle, reference_pins):
+    """The oracle's own row kernels against the reference's compiled row kernels (gstbayerorc-dist.c, -DDISABLE_ORC)
+    under the same frame driver: live where oracle/_ref was built, and always against the md5 of the reference rows'
+    output recorded for the same input (tests/golden/reference_pins.json)."""
+    live = oracle.have_ref_rows()
+    pins = reference_pins["ref_rows"]
+    n = 0
+    for c in ref_rows_cases(oracle):
+        src, w, pat, (r, g, b) = c["src"], c["w"], c["pat"], c["rgb"]
+        a = oracle.bayer2rgb(src, w, pat, r, g, b)
+        assert md5(src) == pins[c["key"]]["in"], c["key"]
+        assert md5(a) == pins[c["key"]]["out"], c["key"]
+        if live:
+            assert np.array_equal(a, oracle.bayer2rgb(src, w, pat, r, g, b, ref_rows=True)), c["key"]
+        n += 1
+    assert n == len(REF_ROWS_SIZES) * 16 == len(pins)
 
 
 def test_simd_row_kernels_equal_reference_rows(oracle):

@@ -21,16 +21,16 @@ step "pytest -m gpu (lab build as the library under test)"
 MIBAYER_LIB_PATH=$R/gst-plugins-bad_amd/libmibayer_lab.so timeout 900 python -m pytest tests -m gpu -q --timeout 600 2>&1 | tail -25 | tee $O/pytest_gpu_lab.log | tail -3
 fi
 step "bench, the driver's arguments"
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | grep '^{' | tail -1 | tee $O/bench.json | cut -c1-400
+timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> $O/bench.err | grep '^{' | tail -1 | tee $O/bench.json | cut -c1-400
 PLAN=$(python -c "import json; print(json.load(open('$O/bench.json'))['config']['plan'])" 2>/dev/null)
 step "rocprofv3 --kernel-trace --stats of the same command, pinned to the plan that line ran ($PLAN)"
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-host-path --no-traffic ${PLAN:+--plan $PLAN} 2>&1 | grep -v "^W20" | tail -1 | cut -c1-300)
+(cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-host-path --no-traffic ${PLAN:+--plan $PLAN} 2>&1 | grep -v "^W20" | tail -1 | cut -c1-300)
 # ... and of EVERY production plan the autotune can return at 4K x 64 (the driver's box picks its own, and
 # whichever it picks, profiles/ must hold THAT kernel's average): the two that have won on some box so far, each pinned
 step "rocprofv3 --kernel-trace --stats, one pass per production plan"
 for plan in lds_4x2_r4_dpp_nt:1:0 lds_1x8_r4_dpp_nt:-1:0 lds_2x4_r4_dpp_nt:1:0; do
   name=$(echo $plan | tr ':-' '_m'); mkdir -p $O/stats_$name
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$name -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-host-path --no-traffic --plan $plan 2>&1 | grep '^{' | tail -1 > $O/stats_$name/bench_line.json)
+  (cd "$TMPDIR" && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$name -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-host-path --no-traffic --plan $plan 2>&1 | grep '^{' | tail -1 > $O/stats_$name/bench_line.json)
   echo "$plan: $(cut -c1-160 $O/stats_$name/bench_line.json)"
 done
 step "one launch per frame: C caller, list launches, kernel traces"
@@ -43,11 +43,11 @@ for arm in 1:d:1 auto:d:1 auto:d:4; do
 done
 find $O -name "t_kernel_trace.csv" -size +3M -delete
 step "force-dist (RCCL group of one rank)"
-timeout 300 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-cpu --no-host-path --no-traffic 2>> $O/bench.err | grep '^{' | tail -1 > $O/bench_force_dist.json
+timeout 300 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --full --no-cpu --no-host-path --no-traffic 2>> $O/bench.err | grep '^{' | tail -1 > $O/bench_force_dist.json
 step "stream mode (configs[4])"
 timeout 300 python bench.py --mode stream 2>> $O/bench.err | grep '^{' | tail -1 > $O/stream_mode.json
 step "eight ranks sharing the one GPU (functional: per_gpu, control-plane fields)"
-timeout 400 python bench.py --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 --no-cpu --no-host-path 2>> $O/bench.err | grep '^{' | tail -1 > $O/eight_ranks_one_gpu.json
+timeout 400 python bench.py --gpus 8 --share-gpu --backend gloo --steps 5 --warmup 2 --full --no-cpu --no-host-path 2>> $O/bench.err | grep '^{' | tail -1 > $O/eight_ranks_one_gpu.json
 step "eight ranks on the one GPU over RCCL (expected to be refused or to fall back: the error path of the N > 1 flow, executed once before a real node does)"
 (timeout 300 python bench.py --gpus 8 --share-gpu --backend nccl --steps 5 --warmup 2 --no-cpu --no-host-path --no-traffic 2>&1 | grep -v "^W20\|^\*\*\*" | tail -25) > $O/eight_ranks_one_gpu_rccl.log 2>&1; grep -c . $O/eight_ranks_one_gpu_rccl.log
 step "host CPU per frame"

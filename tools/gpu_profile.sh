@@ -13,10 +13,10 @@ python -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.build
 echo "== box"; (rocm-smi --showmemorypartition --showcomputepartition --showclocks --showpower --showmaxpower --showserial 2>&1 | grep -v "^$" | head -60) | tee $O/box.txt
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.log
 echo "== pytest gpu"; timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $O/pytest_gpu.log
-echo "== bench (the driver's arguments)"; timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 | tee $O/bench.json | cut -c1-600
+echo "== bench (the driver's arguments)"; timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 | tee $O/bench.json | cut -c1-600
 cd /tmp
 echo "== rocprof stats (same command as the bench line, fewer steps)"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-host-path --no-traffic 2>&1 | grep -v "^W20" | tail -1 | cut -c1-300
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o $TAG -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-host-path --no-traffic 2>&1 | grep -v "^W20" | tail -1 | cut -c1-300
 # HBM-side traffic, separate --pmc passes, for the THREE block orders the autotuner chooses between
 # (forced with MIBAYER_XCD_BAND, autotune off), plus the calibration probe
 for c in FETCH_SIZE WRITE_SIZE; do

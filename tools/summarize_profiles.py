@@ -76,7 +76,7 @@ if os.path.exists(bench):
 stats = glob.glob(os.path.join(src, "stats", "*kernel_stats.csv"))
 if stats:
     shutil.copy(stats[0], os.path.join(dst, "%s_kernel_stats.csv" % tag))
-    lines += ["## `rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-host-path --no-traffic "
+    lines += ["## `rocprofv3 --kernel-trace --stats -- python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-host-path --no-traffic "
               "--plan <config.plan of the line above>` (the driver's arguments, pinned to the plan the unprofiled line ran, so "
               "the dominant kernel of this table IS that line's kernel)", "",
               "| kernel | calls | avg ns | min ns | max ns | % |", "|---|---:|---:|---:|---:|---:|"]
@@ -101,7 +101,7 @@ if stats:
 per_plan = sorted(glob.glob(os.path.join(src, "stats_lds_*")))
 if per_plan:
     lines += ["## `rocprofv3 --kernel-trace --stats`, one pass per production plan (`bench.py --gpus 1 --steps 20 --warmup 5 "
-              "--no-cpu --no-host-path --no-traffic --plan <plan>`)", "",
+              "--full --no-cpu --no-host-path --no-traffic --plan <plan>`)", "",
               "Every plan `mibayer_autotune` has returned for 4K x 64 on some box, each pinned: the driver's box measures its own "
               "plan, and the kernel behind its `roofline` is one of these rows.  Timed = the 20 dispatches of the timed region; "
               "GB/s = 2 654 208 000 B / avg; the bench line is the same process's own HIP-event figure.", "",
