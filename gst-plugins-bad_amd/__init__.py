@@ -36,6 +36,11 @@ FORMATS = {
     "RGBA": (0, 1, 2), "ARGB": (1, 2, 3), "BGRA": (2, 1, 0), "ABGR": (3, 2, 1),
 }
 
+# 16-bit-per-channel output (MIBAYER_FLAG_DST_16BIT): (r_off, g_off, b_off) in 16-bit CHANNELS of the 8-byte pixel.
+# ARGB64 is the one the GStreamer video library of the element knows; the other three are the same layouts as above
+FORMATS16 = {"ARGB64": (1, 2, 3), "RGBA64": (0, 1, 2), "BGRA64": (2, 1, 0), "ABGR64": (3, 2, 1)}
+SRC_BITS = (10, 12, 14, 16)     # MIBAYER_FLAG_SRC_BITS(n) values besides 0 (the 8-bit mosaic)
+
 PLAN_DEFAULT, PLAN_MEASURED, PLAN_CACHED, PLAN_SET = 0, 1, 2, 3
 FRAME_QUEUES = 4                # MIBAYER_FRAME_QUEUES
 OK = 0
@@ -75,6 +80,21 @@ MAX_SHARDS = 16
 FLAG_HIPGRAPH = 1
 FLAG_RGB2BAYER = 2
 FLAG_HIPGRAPH_CHAIN = 4
+FLAG_SRC_BITS_MASK = 0x1F << 8
+FLAG_SRC_BIG_ENDIAN = 1 << 13
+FLAG_DST_16BIT = 1 << 14
+FLAG_DST_BIG_ENDIAN = 1 << 15
+
+
+def FLAG_SRC_BITS(n):
+    """MIBAYER_FLAG_SRC_BITS(n): 16-bit-word samples with n significant bits (n = 0: the 8-bit mosaic)."""
+    return (int(n) << 8) & 0xFFFFFFFF
+
+
+def deep_flags(bits=0, src_big_endian=False, out16=False, dst_big_endian=False):
+    """cfg.flags of a deep context (include/mibayer.h, MIBAYER_FLAG_SRC_BITS); no validation here, the library does it."""
+    return (FLAG_SRC_BITS(bits) | (FLAG_SRC_BIG_ENDIAN if src_big_endian else 0)
+            | (FLAG_DST_16BIT if out16 else 0) | (FLAG_DST_BIG_ENDIAN if dst_big_endian else 0))
 
 
 class HostStats(ctypes.Structure):
@@ -263,8 +283,15 @@ def _ptr(a):
 
 
 def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0, device=-1,
-             inflight=0, variant=0, flags=0):
-    r, g, b = FORMATS[fmt] if isinstance(fmt, str) else fmt
+             inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False):
+    """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
+    name implies out16"""
+    if isinstance(fmt, str) and fmt in FORMATS16:
+        out16 = True
+        r, g, b = FORMATS16[fmt]
+    else:
+        r, g, b = FORMATS[fmt] if isinstance(fmt, str) else fmt
+    flags |= deep_flags(bits, src_big_endian, out16, dst_big_endian)
     pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
     return Cfg(ctypes.sizeof(Cfg), width, height, src_stride, dst_stride, pat, r, g, b,
                device, inflight, variant, flags)
@@ -273,10 +300,11 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
 class Pool:
     """Round-robin frame sharding over HIP devices (mibayer_pool): frame g -> devices[g % N]."""
 
-    def __init__(self, devices, width, height, pattern="bggr", fmt="RGBx", inflight=2, flags=0):
+    def __init__(self, devices, width, height, pattern="bggr", fmt="RGBx", inflight=2, flags=0, **deep):
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= (make_cfg)"""
         pc = PoolCfg()
         pc.struct_size = ctypes.sizeof(PoolCfg)
-        pc.stream = make_cfg(width, height, pattern, fmt, inflight=inflight, flags=flags)
+        pc.stream = make_cfg(width, height, pattern, fmt, inflight=inflight, flags=flags, **deep)
         pc.ndevices = len(devices)
         for i, d in enumerate(devices):
             pc.devices[i] = d
@@ -363,8 +391,10 @@ class Context:
     """
 
     def __init__(self, width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0,
-                 device=-1, inflight=0, variant=0, flags=0):
-        cfg = make_cfg(width, height, pattern, fmt, src_stride, dst_stride, device, inflight, variant, flags)
+                 device=-1, inflight=0, variant=0, flags=0, **deep):
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= (make_cfg); a deep context takes its source as
+        bytes or as any integer array whose bytes are the frame (uint16 words)"""
+        cfg = make_cfg(width, height, pattern, fmt, src_stride, dst_stride, device, inflight, variant, flags, **deep)
         self._h = _vp()
         _check(lib().mibayer_create(ctypes.byref(cfg), ctypes.byref(self._h)), "mibayer_create")
         out = Cfg()
@@ -375,6 +405,7 @@ class Context:
         self.src_bytes = out.src_stride * out.height
         self.dst_bytes = out.dst_stride * out.height
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
+        self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT))
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
@@ -397,13 +428,18 @@ class Context:
     # -- host path --------------------------------------------------------------------------
     def process_host(self, src, dst=None):
         """src: uint8 array of src_stride*height bytes -> (height, dst_stride) uint8."""
-        src = np.ascontiguousarray(src, dtype=np.uint8)
+        src = self._src_bytes(src)
         assert src.size == self.src_bytes, (src.size, self.src_bytes)
         if dst is None:
             dst = np.full((self.height, self.dst_stride), 0xA5, np.uint8)
         assert dst.size == self.dst_bytes and dst.flags.c_contiguous
         _check(lib().mibayer_process_host(self._h, _ptr(src), _ptr(dst)), "mibayer_process_host")
         return dst
+
+    def _src_bytes(self, src):
+        if self.deep and isinstance(src, np.ndarray) and src.dtype != np.uint8:
+            return np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+        return np.ascontiguousarray(src, dtype=np.uint8)
 
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_submit")
@@ -575,6 +611,8 @@ class Context:
     def process_batch_via_device(self, frames):
         """frames: (N, height, src_stride) uint8 on the host -> (N, height, dst_stride) uint8,
         through ONE device-resident batch launch (mibayer_process_device)."""
+        if self.deep and frames.dtype != np.uint8:
+            frames = np.ascontiguousarray(frames).view(np.uint8).reshape(frames.shape[0], -1)
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         n = frames.shape[0]
         assert frames[0].size == self.src_bytes

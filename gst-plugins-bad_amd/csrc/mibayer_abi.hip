@@ -288,6 +288,12 @@ struct mibayer_ctx {
   uint32_t sel[4];
   int swap_rows = 0;
   bool inverse = false;                 /* MIBAYER_FLAG_RGB2BAYER */
+  /* deep samples (MIBAYER_FLAG_SRC_BITS / _DST_16BIT ...): one kernel shape (bayer2rgb_deep_kernel), no plans; the
+   * host path runs without graphs, as rgb2bayer does */
+  bool deep = false;
+  bool deep_in8 = false;                /* 8-bit mosaic, 16-bit output */
+  bool deep_out16 = false;
+  DeepParams deep_args;                 /* the launch-independent fields, made at create */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -723,6 +729,74 @@ static void make_plan (mibayer_ctx *c)
   plan_selectors (c->cfg, c->sel, c->swap_rows);
 }
 
+/* Deep samples: the kernel arguments that follow from the cfg (bayer2rgb_deep_kernel, mibayer_kernels.hip).  8-bit
+ * output reuses the 8-bit path's selectors (c->sel); 16-bit output pixel k of a pair is two dwords, each a v_perm of
+ * {M = [R'_k, B'_k], G pair word}: bytes 4,5 = R', 6,7 = B', 2h,2h+1 = G of pixel parity h, 0x0d = 0xff (alpha),
+ * R' / B' on the channel offsets swapped for rggb / gbrg like the 8-bit path, byte pairs swapped for big-endian. */
+static void make_deep_plan (mibayer_ctx *c)
+{
+  const mibayer_cfg &f = c->cfg;
+  const uint32_t bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
+  const int depth = bits ? (int) bits : 8;
+  c->deep_in8 = bits == 0;
+  c->deep_out16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
+  DeepParams &q = c->deep_args;
+  q = DeepParams ();
+  q.width = f.width;
+  q.height = f.height;
+  q.src_stride = f.src_stride;
+  q.dst_stride = f.dst_stride;
+  q.dn_last = f.height >= 4 ? f.height - 4 : 1;        /* gstbayer2rgb.c:430-447 */
+  q.swap_rows = c->swap_rows;
+  q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
+  q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
+  q.out_shift = c->deep_out16 ? 16 - depth : depth - 8;
+  for (int k = 0; k < 4; k++)
+    q.sel[k] = c->sel[k];
+  int rp = f.r_off, bp = f.b_off;
+  if (f.pattern == MIBAYER_RGGB || f.pattern == MIBAYER_GBRG) {
+    rp = f.b_off;
+    bp = f.r_off;
+  }
+  const bool be = (f.flags & MIBAYER_FLAG_DST_BIG_ENDIAN) != 0;
+  for (int h = 0; h < 2; h++)
+    for (int d = 0; d < 2; d++) {
+      uint32_t s = 0;
+      for (int slot = 0; slot < 2; slot++) {
+        const int ch = 2 * d + slot;
+        uint32_t lo, hi;                /* selector bytes of the value's low / high byte */
+        if (ch == rp) {
+          lo = 4;
+          hi = 5;
+        } else if (ch == bp) {
+          lo = 6;
+          hi = 7;
+        } else if (ch == f.g_off) {
+          lo = (uint32_t) (2 * h);
+          hi = lo + 1;
+        } else {
+          lo = hi = 0x0d;
+        }
+        if (be) {
+          const uint32_t t = lo;
+          lo = hi;
+          hi = t;
+        }
+        s |= (lo << (16 * slot)) | (hi << (16 * slot + 8));
+      }
+      q.sel16[h][d] = s;
+    }
+}
+
+/* one launch of the deep kernel: frames at q.src / q.dst + f * frame bytes or the q.nlist frames of q.src_list /
+ * q.dst_list, all of them or chunks [chunk0, chunk0 + nchunks) of kDeepRows rows (host-path bands) */
+static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes, hipStream_t stream,
+    long long chunk0 = 0, long long nchunks = -1)
+{
+  HIP_TRY (launch_deep (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
+  return MIBAYER_OK;
+}
+
 static bool aligned16 (const void *p)
 {
   return (((uintptr_t) p) & 15u) == 0;
@@ -887,6 +961,16 @@ static int launch (const mibayer_ctx *c, const void *d_src,
 {
   if (nframes == 0 || ntile_rows == 0)
     return MIBAYER_OK;
+  if (c->deep) {                /* tile rows = chunks of kDeepRows rows */
+    DeepParams q = c->deep_args;
+    q.src = (const uint8_t *) d_src;
+    q.dst = (uint8_t *) d_dst;
+    q.src_frame_bytes = src_frame_bytes;
+    q.dst_frame_bytes = dst_frame_bytes;
+    q.nlist = 0;
+    return ntile_rows >= 0 ? launch_deep_kernel (c, q, nframes, stream, tile_row0, ntile_rows)
+        : launch_deep_kernel (c, q, nframes, stream);
+  }
   if (c->inverse) {
     const mibayer_cfg &f = c->cfg;
     R2BParams q;
@@ -1041,7 +1125,18 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   mibayer_cfg f = *in;
   if (f.pattern < MIBAYER_BGGR || f.pattern > MIBAYER_RGGB)
     return MIBAYER_ERR_ARG;
-  if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN))
+  constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
+      | MIBAYER_FLAG_DST_BIG_ENDIAN;
+  if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags))
+    return MIBAYER_ERR_ARG;
+  const uint32_t src_bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
+  if ((f.flags & kDeepFlags) && (f.flags & MIBAYER_FLAG_RGB2BAYER))
+    return MIBAYER_ERR_ARG;                     /* high-bit rgb2bayer does not exist */
+  if (src_bits != 0 && src_bits != 10 && src_bits != 12 && src_bits != 14 && src_bits != 16)
+    return MIBAYER_ERR_ARG;
+  if ((f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) && src_bits == 0)
+    return MIBAYER_ERR_ARG;
+  if ((f.flags & MIBAYER_FLAG_DST_BIG_ENDIAN) && !(f.flags & MIBAYER_FLAG_DST_16BIT))
     return MIBAYER_ERR_ARG;
   if ((f.flags & MIBAYER_FLAG_HIPGRAPH_CHAIN) && !(f.flags & MIBAYER_FLAG_HIPGRAPH))
     return MIBAYER_ERR_ARG;
@@ -1071,6 +1166,8 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     *out = f;
     return MIBAYER_OK;
   }
+  if ((f.flags & kDeepFlags) && f.variant != 0)
+    return MIBAYER_ERR_ARG;                     /* one kernel shape: no variants */
   if (f.variant < 0 || f.variant >= variant_count ())
     return MIBAYER_ERR_ARG;
   if (f.inflight < 0 || f.inflight > 64)
@@ -1079,13 +1176,18 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     return MIBAYER_ERR_GEOMETRY;
   if (f.width > (1 << 28) || f.height > (1 << 28))
     return MIBAYER_ERR_GEOMETRY;
-  if (f.src_stride == 0)
-    f.src_stride = (f.width + 3) & ~3;  /* GST_ROUND_UP_4, gstbayer2rgb.c:477 */
-  if (f.dst_stride == 0)
-    f.dst_stride = 4 * f.width;         /* gstbayer2rgb.c:344 */
-  if (f.src_stride < ((f.width + 3) & ~3) || (f.src_stride & 3))
+  /* deep samples: 2 B per sample, 8 B per output pixel (16-bit rows of a width this large would pass 2^31 bytes) */
+  const int src_row = src_bits ? 2 * f.width : (f.width + 3) & ~3;
+  const bool dst16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
+  if ((src_bits || dst16) && f.width > (1 << 26))
     return MIBAYER_ERR_GEOMETRY;
-  if (f.dst_stride < 4 * f.width || (f.dst_stride & 3))
+  if (f.src_stride == 0)
+    f.src_stride = src_row;             /* GST_ROUND_UP_4, gstbayer2rgb.c:477 */
+  if (f.dst_stride == 0)
+    f.dst_stride = (dst16 ? 8 : 4) * f.width;   /* gstbayer2rgb.c:344 */
+  if (f.src_stride < src_row || (f.src_stride & 3))
+    return MIBAYER_ERR_GEOMETRY;
+  if (f.dst_stride < (dst16 ? 8 : 4) * f.width || (f.dst_stride & (dst16 ? 7 : 3)))
     return MIBAYER_ERR_GEOMETRY;
   if (!layout_known (f.r_off, f.g_off, f.b_off))
     return MIBAYER_ERR_LAYOUT;
@@ -1129,6 +1231,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->src_bytes = (size_t) f.src_stride * f.height;
   c->dst_bytes = (size_t) f.dst_stride * f.height;
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
+  c->deep = (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1145,7 +1248,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
    *  - rows at an 8-byte phase (width % 4 == 2): every lane's store straddles a 16-byte boundary -> write-back
    *    stores + one chunk of the batch per XCD, where the L2 puts the pieces together (plain_store_twin).
    * mibayer_autotune() times all store policies, and the shifted arm, against each other. */
-  c->rows_off_sector = !c->inverse && (f.dst_stride % 64) != 0;
+  c->rows_off_sector = !c->inverse && !c->deep && (f.dst_stride % 64) != 0;
   if (c->rows_off_sector && f.variant == 0 && f.width > pb.var->tile_w) {
     if (f.dst_stride % 16 == 0) {
       pb.var = &variant (hybrid_store_twin (resolve_variant (0, f.width)));
@@ -1155,7 +1258,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
       pb.band = -1;
     }
   }
-  if (f.variant == 0 && !c->inverse && !c->rows_off_sector) {
+  if (f.variant == 0 && !c->inverse && !c->deep && !c->rows_off_sector) {
     int kv = 0, kb = 0;
     if (known_width_plan (f.width, &kv, &kb)) {         /* common sensor widths with a measured winner */
       pb.var = &variant (kv);
@@ -1165,7 +1268,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   /* One frame per launch (PLAN_FRAME): the same plan, except that for sector-aligned geometries "auto" takes the
    * shape whose grid needs the fewest rounds of workgroups (frame_class_variant) */
   c->plan[PLAN_FRAME] = pb;
-  if (f.variant == 0 && !c->inverse && !c->rows_off_sector)
+  if (f.variant == 0 && !c->inverse && !c->deep && !c->rows_off_sector)
     c->plan[PLAN_FRAME] = Plan { &variant (frame_class_variant (f.width, f.height, c->num_cus * 4)), INT32_MIN, 0,
       MIBAYER_PLAN_DEFAULT };
   /* ... and for wide rows at an 8-byte phase (width % 4 == 2: 3838, 2046, 1366 px) the batch class's answer -- write-back
@@ -1219,6 +1322,8 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
     make_inverse_plan (c);
   else
     make_plan (c);
+  if (c->deep)
+    make_deep_plan (c);
   c->host_bands = choose_host_bands (c);
 
   DeviceGuard guard (dev);
@@ -1452,7 +1557,7 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   int rc = validate (cfg, &f);
   if (rc != MIBAYER_OK)
     return rc;
-  if (f.flags & MIBAYER_FLAG_RGB2BAYER)
+  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -1499,7 +1604,7 @@ extern "C" int mibayer_launch_geometry (const mibayer_ctx *c, int nframes,
     int *tile_w, int *tile_h, int *tiles_x, int64_t *tile_rows, int *band,
     int64_t *grid_blocks)
 {
-  if (!c || nframes < 0)
+  if (!c || nframes < 0 || c->deep)
     return MIBAYER_ERR_ARG;
   KParams p;
   KernelFn kern;
@@ -1666,12 +1771,12 @@ static int choose_host_bands (const mibayer_ctx *c)
     want = atoi (e);
   if (want > kMaxHostBands)
     want = kMaxHostBands;
-  const size_t big_side = c->inverse ? c->src_bytes : c->dst_bytes;     /* the 4 B/px frame */
-  if (want < 2 || plan_for (c, 1).var->persistent
+  const size_t big_side = c->inverse ? c->src_bytes : c->dst_bytes;     /* the 4 (8) B/px frame */
+  if (want < 2 || (!c->deep && plan_for (c, 1).var->persistent)
       || big_side < ((size_t) 16 << 20))        /* below ~4K the extra enqueues cost more
                                                    than the overlap gains (1080p: -10 %) */
     return 1;
-  const int th = c->inverse ? kInverseBandUnit : plan_for (c, 1).var->tile_h;
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? kDeepRows : plan_for (c, 1).var->tile_h;
   const int tiles_y = (c->cfg.height + th - 1) / th;
   while (want > 1) {
     const int per = (tiles_y + want - 1) / want;        /* tile rows per band */
@@ -1688,7 +1793,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     uint8_t *dst, size_t row_bytes)
 {
   const mibayer_cfg &f = c->cfg;
-  const int th = c->inverse ? kInverseBandUnit : plan_for (c, 1).var->tile_h;
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? kDeepRows : plan_for (c, 1).var->tile_h;
   const int halo = c->inverse ? 0 : 1;  /* rgb2bayer has no neighbourhood */
   const int tiles_y = (f.height + th - 1) / th;
   const int nb = c->host_bands;
@@ -1853,7 +1958,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 static size_t written_row_bytes (const mibayer_ctx *c)
 {
   return c->inverse ? (size_t) ((c->cfg.width + 3) & ~3)
-      : (size_t) 4 * c->cfg.width;
+      : (size_t) (c->deep_out16 ? 8 : 4) * c->cfg.width;
 }
 
 static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
@@ -1866,7 +1971,7 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
     return MIBAYER_ERR_BUSY;
   Slot &s = c->ring[(size_t) c->head];
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
-  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse;
+  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep;
   if (want_graph && c->graph_mode == 1
       && (size_t) c->cfg.dst_stride == row_bytes) {
     rc = graph_submit (c, s, src, dst);
@@ -2196,6 +2301,22 @@ extern "C" int mibayer_process_device_list (mibayer_ctx *c,
     return MIBAYER_ERR_HIP;
   Range r ("mibayer:process_device_list");
   mark_dirty (c, (hipStream_t) hip_stream);
+  if (c->deep) {
+    for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
+      DeepParams q = c->deep_args;
+      q.src = nullptr;
+      q.dst = nullptr;
+      q.nlist = nframes - f0 < kMaxList ? nframes - f0 : kMaxList;
+      for (int k = 0; k < q.nlist; k++) {
+        q.src_list[k] = (const uint8_t *) d_srcs[f0 + k];
+        q.dst_list[k] = (uint8_t *) d_dsts[f0 + k];
+      }
+      const int rc = launch_deep_kernel (c, q, q.nlist, (hipStream_t) hip_stream);
+      if (rc != MIBAYER_OK)
+        return rc;
+    }
+    return MIBAYER_OK;
+  }
   if (c->inverse) {
     /* the sibling direction (reference loop gst/bayer/gstrgb2bayer.c:254-268): up to kMaxList separately allocated
      * frames per launch of the flat kernel; the tile kernel (MIBAYER_R2B_FLAT=0, tuning) has no table and goes
@@ -2423,7 +2544,7 @@ bool plan_key_is (const PlanEntry &e, const mibayer_ctx *c, int klass)
 
 void plan_cache_store (const mibayer_ctx *c, int klass)
 {
-  if (!plan_cache_enabled () || c->inverse || c->cfg.variant != 0)
+  if (!plan_cache_enabled () || c->inverse || c->deep || c->cfg.variant != 0)
     return;
   std::lock_guard<std::mutex> lk (g_plan_mu);
   PlanEntry *slot = nullptr;
@@ -2445,7 +2566,7 @@ void plan_cache_store (const mibayer_ctx *c, int klass)
 
 static bool plan_cache_load (mibayer_ctx *c)
 {
-  if (!plan_cache_enabled () || c->inverse || c->cfg.variant != 0)
+  if (!plan_cache_enabled () || c->inverse || c->deep || c->cfg.variant != 0)
     return false;
   std::lock_guard<std::mutex> lk (g_plan_mu);
   bool hit = false;
@@ -2642,7 +2763,7 @@ extern "C" int mibayer_autotune (mibayer_ctx *c, const void *d_src,
     size_t src_frame_bytes, void *d_dst, size_t dst_frame_bytes, int nframes,
     char *report, size_t report_len)
 {
-  if (!c || !d_src || !d_dst || nframes < 1 || c->inverse)
+  if (!c || !d_src || !d_dst || nframes < 1 || c->inverse || c->deep)
     return MIBAYER_ERR_ARG;
   if (report && report_len)
     report[0] = 0;
@@ -2669,7 +2790,7 @@ extern "C" int mibayer_autotune (mibayer_ctx *c, const void *d_src,
 extern "C" int mibayer_autotune_list (mibayer_ctx *c, const void *const *d_srcs, void *const *d_dsts, int nframes,
     char *report, size_t report_len)
 {
-  if (!c || !d_srcs || !d_dsts || nframes < 1 || c->inverse)
+  if (!c || !d_srcs || !d_dsts || nframes < 1 || c->inverse || c->deep)
     return MIBAYER_ERR_ARG;
   if (report && report_len)
     report[0] = 0;
@@ -2723,7 +2844,7 @@ extern "C" int mibayer_get_plan_for (const mibayer_ctx *c, int nframes, int *var
 
 static int plan_args_ok (const mibayer_ctx *c, int variant_id, int align_stores)
 {
-  if (!c || c->inverse)
+  if (!c || c->inverse || c->deep)
     return MIBAYER_ERR_ARG;
   if (variant_id < 1 || variant_id >= variant_count ())
     return MIBAYER_ERR_ARG;
@@ -3142,7 +3263,7 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     size_t src_frame_bytes, uint32_t first_frame, int nframes, uint32_t seed,
     void *hip_stream)
 {
-  if (!c || !d_src || nframes < 0 || c->inverse)
+  if (!c || !d_src || nframes < 0 || c->inverse || c->deep)
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

@@ -231,6 +231,40 @@ hipError_t launch_rgb2bayer (const R2BParams &p, bool vec16, hipStream_t stream,
  * kernel (p.flat_k > 0); dst8: every destination 8-byte aligned (two items per store allowed) */
 hipError_t launch_rgb2bayer_list (const R2BParams &p, bool vec16, bool dst8, hipStream_t stream);
 
+/* bayer2rgb on deep samples (MIBAYER_FLAG_SRC_BITS / MIBAYER_FLAG_DST_16BIT): 16-bit-word mosaics of 10-16 significant
+ * bits, and/or 16-bit-per-channel output.  One wave owns a strip of 256 pixels x kDeepRows rows ("chunk") */
+constexpr int kDeepRows = 16;
+struct DeepParams {
+  const uint8_t *src;
+  uint8_t *dst;
+  unsigned long long src_frame_bytes;
+  unsigned long long dst_frame_bytes;
+  int width;
+  int height;
+  int src_stride;
+  int dst_stride;
+  int dn_last;                  /* source row standing in for row `height` */
+  int swap_rows;                /* 1 for grbg / gbrg */
+  uint32_t in_sel;              /* v_perm selector on a source dword: identity or a byte swap per 16-bit word */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  int out_shift;                /* 16-bit out: left shift (16 - bits); 8-bit out: right shift (bits - 8) */
+  uint32_t sel[4];              /* 8-bit out: v_perm selectors of output pixel k (mibayer_plan_selectors) */
+  uint32_t sel16[2][2];         /* 16-bit out: [pixel parity][dword of the pixel], over {R'B' word, G word} */
+  /* filled by launch_deep */
+  int groups;                   /* 4-pixel groups per row = ceil (width / 4) */
+  FastDiv div_tiles_x;          /* 256-pixel strips per row */
+  FastDiv div_chunks;           /* chunks per frame */
+  uint32_t chunk0;              /* first chunk of the launch (host-path bands) */
+  uint32_t nwaves;              /* chunks of the launch x strips */
+  int nlist;                    /* list launch: frame f at src_list[f] / dst_list[f] */
+  const uint8_t *src_list[kMaxList];
+  uint8_t *dst_list[kMaxList];
+};
+/* in8: 8-bit mosaic (then out16 is set); out16: 8-byte output pixels.  Chunks [chunk0, chunk0 + nchunks) of the batch
+ * (nchunks < 0: all of p.nlist frames, or of `nframes`) */
+hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
+    long long chunk0 = 0, long long nchunks = -1);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

@@ -1476,6 +1476,283 @@ hipError_t launch_rgb2bayer_list (const R2BParams &p, bool vec16, bool dst8, hip
 }
 
 /* ------------------------------------------------------------------------- */
+/* deep samples: 10-16-bit mosaics in 16-bit words, 16-bit-per-channel output  */
+/* ------------------------------------------------------------------------- */
+/* The closed form of the file header on samples of `bits` significant bits (the word masked to them), every average
+ * at the native depth, the conversion to the output depth last: 16-bit channels v << (16 - bits) (alpha 0xffff),
+ * 8-bit channels v >> (bits - 8) (alpha 255).  An 8-bit mosaic with 16-bit output is bits = 8.
+ *
+ * A lane owns 4 horizontally adjacent pixels as two dwords of two 16-bit samples each (lo = pixels 0,1, hi = 2,3), a
+ * wave a strip of 256 pixels x kDeepRows rows: it loads all kDeepRows + 2 source rows first (the loads of a lane are all
+ * in flight at once), then walks down with the 3-row window (E,O of rows u, j, d) in registers.  Two samples per dword: avg is exact per half without packed
+ * instructions ((a|b) - (((a^b) >> 1) & 0x7fff7fff): no borrow crosses the halves), the output shift cannot cross
+ * them either.  The x-1 / x+4 neighbours come from the adjacent lanes by DPP; lanes 0 and 63 load theirs.  Output
+ * pixels are v_perm_b32 of {R'B' word, G word} with selectors from the host (layout, Bayer order, output byte order):
+ * 16-bit output 32 bytes per lane (two global_store_dwordx4, pieces swapped inside a quad), 8-bit output 16 bytes
+ * (one, streaming).  Rows need only be
+ * dword-aligned (gfx950 vector memory at dword alignment); the partial last group of a width % 4 == 2 row loads one
+ * dword and stores two pixels. */
+
+constexpr uint32_t kLowHalves = 0x0000ffffu;
+
+__device__ __forceinline__ uint32_t avg16x2 (uint32_t a, uint32_t b)
+{
+  return (a | b) - (((a ^ b) >> 1) & 0x7fff7fffu);
+}
+
+/* the source dwords of one row as loaded: a = pixels 0,1 (8-bit mosaic: pixels 0..3), b = pixels 2,3, e = the edge
+ * dword -- the two samples left of the strip in lane 0, right of it in lane 63.  They are converted (byte order, mask,
+ * 8-bit unpack) only where they are used, so that no load waits for another. */
+struct DeepRaw { uint32_t a, b, e; };
+struct DeepLines { uint32_t elo, ehi, olo, ohi; };
+
+/* loads row y of the frame at `base`: lane group g (x0 = 4g) */
+template <bool IN8>
+__device__ __forceinline__ DeepRaw deep_load (const DeepParams &p, const uint8_t *base, int y, int g, int lane)
+{
+  DeepRaw r = { 0u, 0u, 0u };
+  const uint8_t *row = base + (size_t) y * (size_t) p.src_stride;
+  const int x0 = 4 * g;
+  /* one load instruction per register and no branch between a load and its use: a load into a register that another
+   * load of the same row may still be filling would wait for it */
+  if (g < p.groups) {
+    if constexpr (IN8) {
+      r.a = __builtin_nontemporal_load ((const uint32_t *) (row + x0));
+    } else {
+      /* width % 4 == 2, last group: pixels x0, x0+1 only -- the 8 bytes that end with them (x0 >= 4 there);
+       * deep_lines picks them out of b */
+      const u32x2_a4 c = __builtin_nontemporal_load ((const u32x2_a4 *) (row + 2 * x0 - (x0 + 4 <= p.width ? 0 : 4)));
+      r.a = c.x;
+      r.b = c.y;
+    }
+  }
+  const bool left = lane == 0 && x0 > 0 && g < p.groups;        /* samples x0-2, x0-1 */
+  const bool right = lane == 63 && x0 + 4 < p.width;            /* samples x0+4, x0+5 */
+  if (left || right)
+    r.e = *(const uint32_t *) (row + (IN8 ? (left ? x0 - 4 : x0 + 4) : 2 * (left ? x0 - 2 : x0 + 4)));
+  return r;
+}
+
+/* E / O of one row (reference gstbayer2rgb.c:354-381) with the edge columns O[0] = S[1], E[W-1] = S[W-2],
+ * O[W-2] = S[W-3]: first = group 0; lastmode 1 = last group of a width % 4 == 0 row, 2 = of a width % 4 == 2 row.
+ * The samples are masked, in host byte order, two per dword. */
+template <bool IN8>
+__device__ __forceinline__ DeepLines deep_lines (const DeepParams &p, const DeepRaw &raw, int lane, bool first,
+    int lastmode)
+{
+  const bool partial = lastmode == 2;
+  uint32_t lo, hi, e;
+  if constexpr (IN8) {
+    lo = __builtin_amdgcn_perm (raw.a, raw.a, 0x0c010c00u);
+    hi = __builtin_amdgcn_perm (raw.a, raw.a, 0x0c030c02u);
+    e = __builtin_amdgcn_perm (raw.e, raw.e, lane == 0 ? 0x0c030c02u : 0x0c010c00u);
+  } else {
+    const uint32_t a = partial ? raw.b : raw.a;
+    lo = __builtin_amdgcn_perm (a, a, p.in_sel) & p.mask2;
+    hi = partial ? 0u : __builtin_amdgcn_perm (raw.b, raw.b, p.in_sel) & p.mask2;
+    e = __builtin_amdgcn_perm (raw.e, raw.e, p.in_sel) & p.mask2;
+  }
+  const uint32_t left_hi = from_lane_below (e, hi);             /* [S x0-2, S x0-1] */
+  const uint32_t right_lo = from_lane_above (e, lo);            /* [S x0+4, S x0+5] */
+  const uint32_t mid = __builtin_amdgcn_alignbit (hi, lo, 16);                  /* [s1, s2] */
+  const uint32_t lsh = first ? __builtin_amdgcn_alignbit (lo, lo, 16)           /* [s1, s0] */
+      : __builtin_amdgcn_alignbit (lo, left_hi, 16);                            /* [S x0-1, s0] */
+  const uint32_t rsh = __builtin_amdgcn_alignbit (right_lo, hi, 16);           /* [s3, S x0+4] */
+  const uint32_t a_lo = avg16x2 (lsh, lastmode == 2 ? lsh : mid);
+  const uint32_t a_hi = avg16x2 (mid, lastmode == 1 ? mid : rsh);
+  DeepLines l;
+  l.elo = bsel (kLowHalves, lo, a_lo);
+  l.ehi = bsel (kLowHalves, hi, a_hi);
+  l.olo = bsel (kLowHalves, a_lo, lo);
+  l.ohi = bsel (kLowHalves, a_hi, hi);
+  return l;
+}
+
+/* lane k of a quad: s0 = piece k of the quad's first 64 output bytes (lane k>>1, its v0 / v1 for k even / odd),
+ * s1 = piece k of its last 64 (lane 2 + (k>>1)) */
+template <int CTRL>
+__device__ __forceinline__ u32x4 quad_dpp (u32x4 v)
+{
+  u32x4 r;
+  r.x = (uint32_t) __builtin_amdgcn_mov_dpp ((int) v.x, CTRL, 0xf, 0xf, false);
+  r.y = (uint32_t) __builtin_amdgcn_mov_dpp ((int) v.y, CTRL, 0xf, 0xf, false);
+  r.z = (uint32_t) __builtin_amdgcn_mov_dpp ((int) v.z, CTRL, 0xf, 0xf, false);
+  r.w = (uint32_t) __builtin_amdgcn_mov_dpp ((int) v.w, CTRL, 0xf, 0xf, false);
+  return r;
+}
+
+__device__ __forceinline__ void deep_quad_pieces (u32x4 v0, u32x4 v1, int k, u32x4 &s0, u32x4 &s1)
+{
+  constexpr int kLow = 0x50;            /* quad_perm [0,0,1,1]: lane k reads lane k>>1 */
+  constexpr int kHigh = 0xfa;           /* quad_perm [2,2,3,3]: lane k reads lane 2 + (k>>1) */
+  /* every lane runs all four moves (a DPP source lane must be active), then picks */
+  const u32x4 l0 = quad_dpp<kLow> (v0), l1 = quad_dpp<kLow> (v1);
+  const u32x4 h0 = quad_dpp<kHigh> (v0), h1 = quad_dpp<kHigh> (v1);
+  s0 = (k & 1) ? l1 : l0;
+  s1 = (k & 1) ? h1 : h0;
+}
+
+template <bool IN8, bool OUT16>
+__global__ void __launch_bounds__ (256)
+bayer2rgb_deep_kernel (DeepParams p)
+{
+  const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (wave >= p.nwaves)
+    return;
+  const int lane = (int) (threadIdx.x & 63u);
+  const uint32_t crow = fastdiv (wave, p.div_tiles_x);
+  const uint32_t tx = wave - crow * p.div_tiles_x.d;
+  const uint32_t chunk = p.chunk0 + crow;
+  const uint32_t frame = fastdiv (chunk, p.div_chunks);
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kDeepRows;
+  const int y1 = y0 + kDeepRows < p.height ? y0 + kDeepRows : p.height;
+  const uint8_t *src = p.nlist
+      ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
+  uint8_t *dst = p.nlist
+      ? kernarg_table_entry<uint8_t *> (offsetof (DeepParams, dst_list), frame) : p.dst + frame * p.dst_frame_bytes;
+  const int g = (int) tx * 64 + lane;
+  const bool first = g == 0;
+  const int lastmode = g == p.groups - 1 ? ((p.width & 3) ? 2 : 1) : 0;
+  const bool store = g < p.groups;
+  const bool full = 4 * g + 4 <= p.width;
+
+  /* every source row of the chunk is loaded up front (kDeepRows + 2 loads in flight per lane): raw[0] = up(y0),
+   * raw[1 + k] = row y0 + k, and the row past the frame is dn(H-1) (rows past a short last chunk are never used) */
+  DeepRaw raw[kDeepRows + 2];
+#pragma unroll
+  for (int i = 0; i < kDeepRows + 2; i++) {
+    const int r = i == 0 ? (y0 == 0 ? 1 : y0 - 1) : y0 + i - 1;
+    raw[i] = deep_load<IN8> (p, src, r < p.height ? r : p.dn_last, g, lane);
+  }
+  DeepLines up = deep_lines<IN8> (p, raw[0], lane, first, lastmode);
+  DeepLines cur = deep_lines<IN8> (p, raw[1], lane, first, lastmode);
+#pragma unroll
+  for (int k = 0; k < kDeepRows; k++) {
+    const int j = y0 + k;
+    if (j >= y1)
+      break;
+    const DeepLines dn = deep_lines<IN8> (p, raw[k + 2], lane, first, lastmode);
+    /* merge (orc:43-92): T = 0 merge_bg, T = 1 merge_gr */
+    const bool t = ((j & 1) ^ p.swap_rows) != 0;
+    const uint32_t ve_lo = avg16x2 (up.elo, dn.elo), ve_hi = avg16x2 (up.ehi, dn.ehi);
+    const uint32_t vo_lo = avg16x2 (up.olo, dn.olo), vo_hi = avg16x2 (up.ohi, dn.ohi);
+    uint32_t rb_lo, rb_hi, b_lo, b_hi, g_lo, g_hi;      /* R', B', G per pixel pair */
+    if (t) {
+      b_lo = ve_lo;
+      b_hi = ve_hi;
+      rb_lo = cur.olo;
+      rb_hi = cur.ohi;
+      g_lo = bsel (kLowHalves, cur.elo, avg16x2 (vo_lo, cur.elo));
+      g_hi = bsel (kLowHalves, cur.ehi, avg16x2 (vo_hi, cur.ehi));
+    } else {
+      b_lo = cur.elo;
+      b_hi = cur.ehi;
+      rb_lo = vo_lo;
+      rb_hi = vo_hi;
+      g_lo = bsel (kLowHalves, avg16x2 (ve_lo, cur.olo), cur.olo);
+      g_hi = bsel (kLowHalves, avg16x2 (ve_hi, cur.ohi), cur.ohi);
+    }
+    uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
+    if constexpr (OUT16) {
+      const int s = p.out_shift;
+      rb_lo <<= s; rb_hi <<= s; b_lo <<= s; b_hi <<= s; g_lo <<= s; g_hi <<= s;
+      /* M_k = [R'_k, B'_k] */
+      const uint32_t m0 = __builtin_amdgcn_perm (b_lo, rb_lo, 0x05040100u);
+      const uint32_t m1 = __builtin_amdgcn_perm (b_lo, rb_lo, 0x07060302u);
+      const uint32_t m2 = __builtin_amdgcn_perm (b_hi, rb_hi, 0x05040100u);
+      const uint32_t m3 = __builtin_amdgcn_perm (b_hi, rb_hi, 0x07060302u);
+      u32x4 v0, v1;
+      v0.x = __builtin_amdgcn_perm (m0, g_lo, p.sel16[0][0]);
+      v0.y = __builtin_amdgcn_perm (m0, g_lo, p.sel16[0][1]);
+      v0.z = __builtin_amdgcn_perm (m1, g_lo, p.sel16[1][0]);
+      v0.w = __builtin_amdgcn_perm (m1, g_lo, p.sel16[1][1]);
+      v1.x = __builtin_amdgcn_perm (m2, g_hi, p.sel16[0][0]);
+      v1.y = __builtin_amdgcn_perm (m2, g_hi, p.sel16[0][1]);
+      v1.z = __builtin_amdgcn_perm (m3, g_hi, p.sel16[1][0]);
+      v1.w = __builtin_amdgcn_perm (m3, g_hi, p.sel16[1][1]);
+      /* A lane holds 32 contiguous bytes, so two stores straight from its registers would each fill every other
+       * 16 bytes of the wave's 2 KiB.  The four lanes of a quad swap pieces instead (DPP quad_perm): the first store
+       * writes the quad's first 64 bytes, the second its last 64, and write-back stores let the L2 join the two
+       * halves of a 128-byte line.  4K x 16, 12-bit -> ARGB64: 30 % of peak with streaming stores straight from the
+       * registers, 47 % write-back, 41 % swapped + streaming, 50 % swapped + write-back. */
+      const int k = lane & 3;
+      u32x4 s0, s1;
+      deep_quad_pieces (v0, v1, k, s0, s1);
+      const int qg = g - k;                             /* first group of the quad */
+      const int ga = qg + (k >> 1), gb = qg + 2 + (k >> 1);     /* group whose piece k&1 this lane stores */
+      if (ga < p.groups && ((k & 1) == 0 || 4 * ga + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * k) = s0;
+      if (gb < p.groups && ((k & 1) == 0 || 4 * gb + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * k) = s1;
+    } else {
+      const int s = p.out_shift;
+      constexpr uint32_t kLowBytes = 0x00ff00ffu;
+      rb_lo = (rb_lo >> s) & kLowBytes; rb_hi = (rb_hi >> s) & kLowBytes;
+      b_lo = (b_lo >> s) & kLowBytes; b_hi = (b_hi >> s) & kLowBytes;
+      g_lo = (g_lo >> s) & kLowBytes; g_hi = (g_hi >> s) & kLowBytes;
+      /* the 8-bit kernel's operands: M = [r' b' r' b'] of a pixel pair, G = green of pixels 0..3 */
+      const uint32_t m_lo = rb_lo | (b_lo << 8);
+      const uint32_t m_hi = rb_hi | (b_hi << 8);
+      const uint32_t gw = __builtin_amdgcn_perm (g_hi, g_lo, 0x06040200u);
+      u32x4 v;
+      v.x = __builtin_amdgcn_perm (m_lo, gw, p.sel[0]);
+      v.y = __builtin_amdgcn_perm (m_lo, gw, p.sel[1]);
+      v.z = __builtin_amdgcn_perm (m_hi, gw, p.sel[2]);
+      v.w = __builtin_amdgcn_perm (m_hi, gw, p.sel[3]);
+      if (store) {
+        uint8_t *q = out + 16 * (size_t) g;
+        if (full) {
+          __builtin_nontemporal_store (v, (u32x4_a4 *) q);
+        } else {
+          const u32x2_a4 two = { v.x, v.y };
+          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+        }
+      }
+    }
+    up = cur;
+    cur = dn;
+  }
+}
+
+hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
+    long long chunk0, long long nchunks)
+{
+  if (p.width < 4 || p.height < 3 || (p.width & 1) || (in8 && !out16))
+    return hipErrorInvalidValue;
+  DeepParams q = p;
+  q.groups = (p.width + 3) / 4;
+  const int tiles_x = (q.groups + 63) / 64;
+  const long long chunks_per_frame = (p.height + kDeepRows - 1) / kDeepRows;
+  const long long frames = p.nlist > 0 ? p.nlist : nframes;
+  if (p.nlist > kMaxList || frames <= 0)
+    return frames == 0 ? hipSuccess : hipErrorInvalidValue;
+  const long long total = frames * chunks_per_frame;
+  if (nchunks < 0) {
+    chunk0 = 0;
+    nchunks = total;
+  }
+  if (chunk0 < 0 || chunk0 + nchunks > total)
+    return hipErrorInvalidValue;
+  if (nchunks == 0)
+    return hipSuccess;
+  const long long waves = nchunks * tiles_x;
+  if (total > 0x7fffffffLL || waves > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  q.div_tiles_x = make_fastdiv ((uint32_t) tiles_x);
+  q.div_chunks = make_fastdiv ((uint32_t) chunks_per_frame);
+  q.chunk0 = (uint32_t) chunk0;
+  q.nwaves = (uint32_t) waves;
+  const unsigned grid = (unsigned) ((waves + 3) / 4);
+  if (in8)
+    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<true, true>), dim3 (grid), dim3 (256), 0, stream, q);
+  else if (out16)
+    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, true>), dim3 (grid), dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, false>), dim3 (grid), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

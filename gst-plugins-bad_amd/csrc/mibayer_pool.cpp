@@ -281,7 +281,9 @@ struct mibayer_pool {
   size_t redo_rr = 0;
   bool use_helpers = true;      /* MIBAYER_POOL_HELPERS=0: pageable frames on the calling thread */
   bool numa_route = false;      /* the shards' devices span more than one NUMA node */
-  bool inverse = false;         /* MIBAYER_FLAG_RGB2BAYER: the source is the 4 B/px side */
+  bool inverse = false;         /* MIBAYER_FLAG_RGB2BAYER: the source is the 4 B/px side.  A deep context
+                                   (MIBAYER_FLAG_SRC_BITS / _DST_16BIT) keeps the destination as the big side:
+                                   4 or 8 B/px out against at most 2 B/px in */
   std::unordered_map<const void *, int> node_of;        /* NUMA node of buffers seen so far (pools recycle them) */
   /* frames lost on a device that ran into the wait deadline: their buffers are the device's until it settles */
   struct Lost { void *tag; int shard; };
@@ -647,7 +649,8 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       continue;
     const size_t turn = idx;
     if (pool->numa_route) {
-      /* the live shard next to the frame's big buffer, if taking it keeps the rotation balanced */
+      /* the live shard next to the frame's big buffer, if taking it keeps the rotation balanced (the destination
+       * of bayer2rgb at every depth: 16-bit samples in, 8 B/px out is still the bigger side) */
       const void *big = pool->inverse ? (const void *) src : (const void *) dst;
       int node;
       auto it = pool->node_of.find (big);

@@ -22,12 +22,24 @@ typedef GstMiBayerElementClass GstBayer2RGBClass;
 
 GType gst_bayer2rgb_get_type (void);
 
-/* identical strings to the reference, order matters: the first src format
- * (RGBx) is what default negotiation fixates to */
+/* identical strings to the reference in the FIRST structure of each template,
+ * order matters: the first src format (RGBx) is what default negotiation
+ * fixates to -- for deep mosaics too.  The second structures add deep samples
+ * (include/mibayer.h, MIBAYER_FLAG_SRC_BITS): 16-bit words of 10-16 significant
+ * bits in either byte order, spelled <order><bits><le|be> like newer
+ * GStreamer's bayer caps, and ARGB64, the one 16-bit-per-channel RGB format of
+ * the GStreamer 1.14 video library (native endian: little-endian here). */
 #define BAYER2RGB_SRC_CAPS \
-  GST_VIDEO_CAPS_MAKE ("{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }")
+  GST_VIDEO_CAPS_MAKE ("{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }") \
+  "; " GST_VIDEO_CAPS_MAKE ("ARGB64")
+#define BAYER2RGB_DEEP_ORDER(o) \
+  o "10le," o "10be," o "12le," o "12be," o "14le," o "14be," o "16le," o "16be"
 #define BAYER2RGB_SINK_CAPS \
   "video/x-bayer,format=(string){bggr,grbg,gbrg,rggb}," \
+  "width=(int)[1,MAX],height=(int)[1,MAX],framerate=(fraction)[0/1,MAX]; " \
+  "video/x-bayer,format=(string){" BAYER2RGB_DEEP_ORDER ("bggr") "," \
+  BAYER2RGB_DEEP_ORDER ("grbg") "," BAYER2RGB_DEEP_ORDER ("gbrg") "," \
+  BAYER2RGB_DEEP_ORDER ("rggb") "}," \
   "width=(int)[1,MAX],height=(int)[1,MAX],framerate=(fraction)[0/1,MAX]"
 
 MI_DEFINE_ELEMENT_TYPE (GstBayer2RGB, gst_bayer2rgb, MIBAYER_TYPE_NAME ("Bayer2RGB"));

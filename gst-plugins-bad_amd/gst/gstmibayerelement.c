@@ -336,6 +336,9 @@ element_clear_negotiation (GstMiBayerElement * self)
   self->g_off = 0;
   self->b_off = 0;
   self->format = MIBAYER_BGGR;
+  self->src_bits = 0;
+  self->src_big_endian = FALSE;
+  self->out16 = FALSE;
   gst_video_info_init (&self->info);
 }
 
@@ -376,10 +379,20 @@ element_ndevices (GstMiBayerElement * self)
   return element_parse_devices (self, &pc) ? pc.ndevices : 1;
 }
 
-/* `video_stride` is the mapped stride of the 4-byte-per-pixel frame: the
- * destination stride of bayer2rgb (reference gstbayer2rgb.c:476), the source
- * stride of rgb2bayer (gstrgb2bayer.c:256).  The mosaic rows are always
- * GST_ROUND_UP_4 (width) apart (gstbayer2rgb.c:477, gstrgb2bayer.c:255). */
+/* bytes of a mosaic row: GST_ROUND_UP_4 (width) for 8-bit samples
+ * (gstbayer2rgb.c:477, gstrgb2bayer.c:255), GST_ROUND_UP_4 (2 * width) for
+ * 16-bit words (bayer2rgb's deep caps) */
+static gint
+element_mosaic_stride (GstMiBayerElement * self)
+{
+  return self->src_bits ? GST_ROUND_UP_4 (2 * self->width)
+      : GST_ROUND_UP_4 (self->width);
+}
+
+/* `video_stride` is the mapped stride of the 4-byte-per-pixel frame (8 bytes
+ * for ARGB64): the destination stride of bayer2rgb (reference
+ * gstbayer2rgb.c:476), the source stride of rgb2bayer (gstrgb2bayer.c:256).
+ * The mosaic rows are element_mosaic_stride () apart. */
 static gboolean
 element_ensure_pool (GstMiBayerElement * self, gint video_stride)
 {
@@ -426,7 +439,7 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
     pc.stream.src_stride = video_stride;
     pc.stream.dst_stride = GST_ROUND_UP_4 (self->width);
   } else {
-    pc.stream.src_stride = GST_ROUND_UP_4 (self->width);
+    pc.stream.src_stride = element_mosaic_stride (self);
     pc.stream.dst_stride = video_stride;
   }
   pc.stream.pattern = self->format;
@@ -435,7 +448,10 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
   pc.stream.b_off = self->b_off;
   pc.stream.inflight = self->act.inflight;
   pc.stream.flags = (self->act.use_hipgraph ? MIBAYER_FLAG_HIPGRAPH : 0)
-      | (inverse ? MIBAYER_FLAG_RGB2BAYER : 0);
+      | (inverse ? MIBAYER_FLAG_RGB2BAYER : 0)
+      | MIBAYER_FLAG_SRC_BITS (self->src_bits)
+      | (self->src_big_endian ? MIBAYER_FLAG_SRC_BIG_ENDIAN : 0)
+      | (self->out16 ? MIBAYER_FLAG_DST_16BIT : 0);
   if (!element_parse_devices (self, &pc)) {
     element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
         g_strdup_printf ("%s: cannot parse devices=\"%s\"", LABEL (self),
@@ -610,6 +626,51 @@ element_transform_caps (GstBaseTransform * base, GstPadDirection direction,
   return result;
 }
 
+/* "bggr" (reference gstbayer2rgb.c:241-250) or a deep order "<order><bits><le|be>",
+ * bits 10, 12, 14 or 16 (bayer2rgb's second sink structure): FALSE for anything
+ * else.  Any out pointer may be NULL. */
+static gboolean
+element_parse_bayer_format (const gchar * fmt, gint * pattern, gint * bits,
+    gboolean * big_endian)
+{
+  static const struct
+  {
+    const gchar *name;
+    gint pattern;
+  } orders[] = {
+    {"bggr", MIBAYER_BGGR}, {"gbrg", MIBAYER_GBRG},
+    {"grbg", MIBAYER_GRBG}, {"rggb", MIBAYER_RGGB}
+  };
+  guint i;
+  gint b = 0;
+  gboolean be = FALSE;
+
+  if (fmt == NULL || strlen (fmt) < 4)
+    return FALSE;
+  for (i = 0; i < G_N_ELEMENTS (orders); i++) {
+    if (strncmp (fmt, orders[i].name, 4) == 0)
+      break;
+  }
+  if (i == G_N_ELEMENTS (orders))
+    return FALSE;
+  if (fmt[4] != '\0') {
+    if (strlen (fmt) != 8 || (strcmp (fmt + 6, "le") != 0
+            && strcmp (fmt + 6, "be") != 0))
+      return FALSE;
+    b = (fmt[4] - '0') * 10 + (fmt[5] - '0');
+    if (b != 10 && b != 12 && b != 14 && b != 16)
+      return FALSE;
+    be = fmt[6] == 'b';
+  }
+  if (pattern)
+    *pattern = orders[i].pattern;
+  if (bits)
+    *bits = b;
+  if (big_endian)
+    *big_endian = be;
+  return TRUE;
+}
+
 /* reference gstbayer2rgb.c:324-352, gstrgb2bayer.c:161-188 */
 static gboolean
 element_get_unit_size (GstBaseTransform * base, GstCaps * caps, gsize * size)
@@ -623,10 +684,20 @@ element_get_unit_size (GstBaseTransform * base, GstCaps * caps, gsize * size)
         ("Incomplete caps, some required field missing"));
     return FALSE;
   }
-  if (gst_structure_has_name (s, "video/x-raw"))
-    *size = (gsize) w * h * 4;            /* always 32 bits per pixel */
-  else
-    *size = (gsize) GST_ROUND_UP_4 (w) * h;     /* 8-bit mosaic, rows padded to 4 */
+  if (gst_structure_has_name (s, "video/x-raw")) {
+    const gchar *fmt = gst_structure_get_string (s, "format");
+
+    /* 32 bits per pixel, 64 for ARGB64 (bayer2rgb's deep output) */
+    *size = (gsize) w * h * (fmt != NULL && g_str_equal (fmt, "ARGB64") ? 8 : 4);
+  } else {
+    gint bits = 0;
+
+    if (!element_parse_bayer_format (gst_structure_get_string (s, "format"),
+            NULL, &bits, NULL))
+      bits = 0;
+    /* 8-bit mosaic rows padded to 4; 16-bit words per sample for deep ones */
+    *size = (gsize) (bits ? GST_ROUND_UP_4 (2 * w) : GST_ROUND_UP_4 (w)) * h;
+  }
   return TRUE;
 }
 
@@ -634,14 +705,6 @@ element_get_unit_size (GstBaseTransform * base, GstCaps * caps, gsize * size)
 static gboolean
 element_set_caps (GstBaseTransform * base, GstCaps * incaps, GstCaps * outcaps)
 {
-  static const struct
-  {
-    const gchar *name;
-    gint pattern;
-  } orders[] = {
-    {"bggr", MIBAYER_BGGR}, {"gbrg", MIBAYER_GBRG},
-    {"grbg", MIBAYER_GRBG}, {"rggb", MIBAYER_RGGB}
-  };
   GstMiBayerElement *self = ELEMENT (base);
   const gboolean inverse = IS_INVERSE (self);
   GstCaps *bayer_caps = inverse ? outcaps : incaps;
@@ -649,7 +712,8 @@ element_set_caps (GstBaseTransform * base, GstCaps * incaps, GstCaps * outcaps)
   GstStructure *s = gst_caps_get_structure (bayer_caps, 0);
   const gchar *order;
   GstVideoInfo info;
-  guint i;
+  gint pattern, bits;
+  gboolean big_endian;
 
   EL_DEBUG (self, "in caps %" GST_PTR_FORMAT " out caps %"
       GST_PTR_FORMAT, incaps, outcaps);
@@ -671,23 +735,25 @@ element_set_caps (GstBaseTransform * base, GstCaps * incaps, GstCaps * outcaps)
   }
 
   order = gst_structure_get_string (s, "format");
-  if (order == NULL)
+  if (!element_parse_bayer_format (order, &pattern, &bits, &big_endian))
     return FALSE;
-  for (i = 0; i < G_N_ELEMENTS (orders); i++) {
-    if (g_str_equal (order, orders[i].name))
-      break;
-  }
-  if (i == G_N_ELEMENTS (orders))
+  if (inverse && bits)          /* rgb2bayer's templates have 8-bit mosaics only */
     return FALSE;
-  self->format = orders[i].pattern;
+  self->format = pattern;
+  self->src_bits = bits;
+  self->src_big_endian = big_endian;
 
   /* where R, G and B live inside the 4-byte pixel (rgb2bayer's ARGB: 1, 2, 3 =
    * the hard-coded offsets of gstrgb2bayer.c:259-266) */
   if (!gst_video_info_from_caps (&info, raw_caps))
     return FALSE;
-  self->r_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 0);
-  self->g_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 1);
-  self->b_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 2);
+  /* ARGB64 (bayer2rgb's deep output): 16-bit channels, offsets counted in them */
+  self->out16 = GST_VIDEO_INFO_FORMAT (&info) == GST_VIDEO_FORMAT_ARGB64;
+  if (inverse && self->out16)
+    return FALSE;
+  self->r_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 0) / (self->out16 ? 2 : 1);
+  self->g_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 1) / (self->out16 ? 2 : 1);
+  self->b_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 2) / (self->out16 ? 2 : 1);
   self->info = info;
 
   /* geometry changed: the GPU pool is rebuilt on the next buffer, once the
@@ -830,7 +896,7 @@ element_submit (GstMiBayerElement * self, GstBuffer * inbuf, GstBuffer * outbuf,
     g_free (p);
     return GST_FLOW_CUSTOM_ERROR;
   }
-  if (p->mosaic.size < (gsize) GST_ROUND_UP_4 (self->width) * self->height) {
+  if (p->mosaic.size < (gsize) element_mosaic_stride (self) * self->height) {
     element_defer_error (self, GST_STREAM_ERROR, GST_STREAM_ERROR_FORMAT,
         g_strdup_printf ("%s: short %s buffer", LABEL (self),
             inverse ? "output" : "input"),

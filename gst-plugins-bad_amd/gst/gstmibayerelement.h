@@ -32,10 +32,16 @@ struct _GstMiBayerElement
   GstVideoInfo info;            /* the video/x-raw side: output of bayer2rgb, input of rgb2bayer */
   gint width;
   gint height;
-  gint r_off;                   /* byte offset of red inside a 4-byte pixel */
+  gint r_off;                   /* byte offset of red inside a 4-byte pixel (channel of an 8-byte one) */
   gint g_off;
   gint b_off;
   gint format;                  /* mibayer_pattern == reference enum (gstbayer2rgb.c:95-101) */
+  /* deep samples (bayer2rgb only; include/mibayer.h, MIBAYER_FLAG_SRC_BITS): significant bits of a 16-bit-word
+   * mosaic sample (0 = the 8-bit mosaic) and its byte order, and 16-bit output channels (ARGB64: r/g/b_off then
+   * count 16-bit channels) */
+  gint src_bits;
+  gboolean src_big_endian;
+  gboolean out16;
 
   /* additive, optional properties (the reference has none); the defaults give
    * the reference's behaviour: one device, strictly 1-in/1-out synchronous.

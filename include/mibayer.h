@@ -61,6 +61,9 @@ extern "C" {
  * mibayer_device_pci_bus_id.
  * mibayer_get_plan / mibayer_plan_source / mibayer_ctx_variant_name keep describing the batch-class plan,
  * mibayer_set_plan / mibayer_copy_plan pin every class. */
+/* 5, later additive: deep samples -- flags only (MIBAYER_FLAG_SRC_BITS, _SRC_BIG_ENDIAN, _DST_16BIT,
+ * _DST_BIG_ENDIAN: 10-16-bit mosaics in 16-bit words, 16-bit-per-channel output); no struct field and no entry point
+ * was added, and a cfg without them means what it meant. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -148,7 +151,10 @@ typedef struct mibayer_cfg {
                              mibayer_submit(); 0 = default (2)               */
   int32_t variant;        /* kernel variant; 0 = default.  Tuning knob, every
                              variant is bit-exact            */
-  uint32_t flags;         /* MIBAYER_FLAG_* or 0                             */
+  uint32_t flags;         /* MIBAYER_FLAG_* or 0.  Deep samples (16-bit-word
+                             mosaics, 16-bit channels) are flags too, and
+                             change the stride defaults / units above and the
+                             offsets to 16-bit channels: MIBAYER_FLAG_SRC_BITS */
 } mibayer_cfg;
 
 /* Host path: the compute-queue segment of every frame (wait for the upload ->
@@ -174,6 +180,28 @@ typedef struct mibayer_cfg {
  * only.  Measured slower at 4K (the copies of consecutive frames serialise per
  * slot); kept as the A/B arm bench.py reports. */
 #define MIBAYER_FLAG_HIPGRAPH_CHAIN 4u
+
+/* Deep samples (additive within version 5: flags only, mibayer_cfg keeps its fields).  A context with any of the
+ * four flags below is a DEEP context; the algorithm is the one of the 8-bit path on wider integers:
+ *   input   one 16-bit word per sample (little-endian; big-endian with MIBAYER_FLAG_SRC_BIG_ENDIAN), masked to its
+ *           low `bits` bits -- everything above them is ignored; MIBAYER_FLAG_SRC_BITS(0) = the 8-bit mosaic;
+ *   average avg(a,b) = (a+b+1)>>1 on the masked values, at the native depth; nothing is rescaled before the end;
+ *   output  16-bit channels (MIBAYER_FLAG_DST_16BIT, 8-byte pixels): v << (16 - bits), alpha 0xffff, little-endian
+ *           words (big-endian with MIBAYER_FLAG_DST_BIG_ENDIAN); r_off / g_off / b_off count 16-bit CHANNELS 0..3
+ *           in the four layouts of the 8-bit path (ARGB64 = 1,2,3).  Without DST_16BIT the 4-byte formats:
+ *           v >> (bits - 8), truncating, alpha 255.  An 8-bit mosaic with 16-bit output is v << 8.
+ * Strides: 16-bit samples src_stride default 2*width, >= 2*width, multiple of 4; DST_16BIT dst_stride default
+ * 8*width, >= 8*width, multiple of 8.  Geometry as the 8-bit path (even width >= 4, height >= 3).  Any of the four
+ * together with MIBAYER_FLAG_RGB2BAYER, SRC_BITS outside {0, 10, 12, 14, 16} or an endianness flag without its
+ * depth is MIBAYER_ERR_ARG.  Every host / device / list / pool entry point works on a deep context; the host path
+ * accepts MIBAYER_FLAG_HIPGRAPH and runs without graphs (as rgb2bayer does).  mibayer_autotune[_list],
+ * mibayer_fill_synthetic, mibayer_set_plan[_for] and mibayer_plan_selectors return MIBAYER_ERR_ARG: a deep context
+ * has one kernel shape and no plans. */
+#define MIBAYER_FLAG_SRC_BITS(n) ((uint32_t) (n) << 8)
+#define MIBAYER_FLAG_SRC_BITS_MASK (0x1fu << 8)
+#define MIBAYER_FLAG_SRC_BIG_ENDIAN (1u << 13)
+#define MIBAYER_FLAG_DST_16BIT (1u << 14)
+#define MIBAYER_FLAG_DST_BIG_ENDIAN (1u << 15)
 
 typedef struct mibayer_ctx mibayer_ctx;
 
