@@ -84,6 +84,8 @@ FLAG_SRC_BITS_MASK = 0x1F << 8
 FLAG_SRC_BIG_ENDIAN = 1 << 13
 FLAG_DST_16BIT = 1 << 14
 FLAG_DST_BIG_ENDIAN = 1 << 15
+FLAG_MHC = 1 << 16              # Malvar-He-Cutler demosaic instead of the reference's bilinear one
+METHODS = {"bilinear": 0, "mhc": FLAG_MHC}      # the `method` keyword of make_cfg / Context / Pool
 
 
 def FLAG_SRC_BITS(n):
@@ -283,9 +285,13 @@ def _ptr(a):
 
 
 def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0, device=-1,
-             inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False):
+             inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False,
+             method="bilinear"):
     """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
-    name implies out16"""
+    name implies out16.  method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC)"""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, not %r" % (sorted(METHODS), method))
+    flags |= METHODS[method]
     if isinstance(fmt, str) and fmt in FORMATS16:
         out16 = True
         r, g, b = FORMATS16[fmt]
@@ -301,7 +307,7 @@ class Pool:
     """Round-robin frame sharding over HIP devices (mibayer_pool): frame g -> devices[g % N]."""
 
     def __init__(self, devices, width, height, pattern="bggr", fmt="RGBx", inflight=2, flags=0, **deep):
-        """deep: bits= / src_big_endian= / out16= / dst_big_endian= (make_cfg)"""
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= (make_cfg)"""
         pc = PoolCfg()
         pc.struct_size = ctypes.sizeof(PoolCfg)
         pc.stream = make_cfg(width, height, pattern, fmt, inflight=inflight, flags=flags, **deep)
@@ -392,8 +398,8 @@ class Context:
 
     def __init__(self, width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0,
                  device=-1, inflight=0, variant=0, flags=0, **deep):
-        """deep: bits= / src_big_endian= / out16= / dst_big_endian= (make_cfg); a deep context takes its source as
-        bytes or as any integer array whose bytes are the frame (uint16 words)"""
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= (make_cfg); a deep context takes its
+        source as bytes or as any integer array whose bytes are the frame (uint16 words)"""
         cfg = make_cfg(width, height, pattern, fmt, src_stride, dst_stride, device, inflight, variant, flags, **deep)
         self._h = _vp()
         _check(lib().mibayer_create(ctypes.byref(cfg), ctypes.byref(self._h)), "mibayer_create")
@@ -406,6 +412,7 @@ class Context:
         self.dst_bytes = out.dst_stride * out.height
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
         self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT))
+        self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):

@@ -291,7 +291,8 @@ struct mibayer_ctx {
   /* deep samples (MIBAYER_FLAG_SRC_BITS / _DST_16BIT ...): one kernel shape (bayer2rgb_deep_kernel), no plans; the
    * host path runs without graphs, as rgb2bayer does */
   bool deep = false;
-  bool deep_in8 = false;                /* 8-bit mosaic, 16-bit output */
+  bool deep_in8 = false;                /* 8-bit mosaic (16-bit output unless mhc) */
+  bool mhc = false;                     /* MIBAYER_FLAG_MHC: bayer2rgb_mhc_kernel; a deep context, 8-bit ones included */
   bool deep_out16 = false;
   DeepParams deep_args;                 /* the launch-independent fields, made at create */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
@@ -729,6 +730,47 @@ static void make_plan (mibayer_ctx *c)
   plan_selectors (c->cfg, c->sel, c->swap_rows);
 }
 
+/* Malvar-He-Cutler: the site map and output selectors (bayer2rgb_mhc_kernel, mibayer_kernels.hip).  A row's non-green
+ * colour C and the other one D: x = [C, G], y = [D, 0] at output depth, so v_perm bytes 4,5 = C, 6,7 = G, 0,1 = D,
+ * 0x0d = 0xff (alpha).  4-byte output takes the low byte of each value, 16-bit output both, swapped for big-endian. */
+static void make_mhc_selectors (mibayer_ctx *c, int depth)
+{
+  const mibayer_cfg &f = c->cfg;
+  DeepParams &q = c->deep_args;
+  /* top-left 2x2 in raster order: bggr = B G / G R, gbrg = G B / R G, grbg = G R / B G, rggb = R G / G B */
+  q.mhc_green_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_RGGB;
+  q.mhc_red_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_GBRG;
+  q.mhc_max = (1 << depth) - 1;
+  const bool be = (f.flags & MIBAYER_FLAG_DST_BIG_ENDIAN) != 0;
+  for (int rk = 0; rk < 2; rk++) {
+    const int r_lo = rk == 0 ? 4 : 0, b_lo = rk == 0 ? 0 : 4;  /* rk 0: C = R, D = B */
+    if (!c->deep_out16) {
+      uint32_t s = 0;
+      for (int ch = 0; ch < 4; ch++) {
+        const uint32_t b = ch == f.r_off ? r_lo : ch == f.b_off ? b_lo : ch == f.g_off ? 6 : 0x0d;
+        s |= b << (8 * ch);
+      }
+      q.mhc_sel[rk][0] = q.mhc_sel[rk][1] = s;
+      continue;
+    }
+    for (int d = 0; d < 2; d++) {
+      uint32_t s = 0;
+      for (int slot = 0; slot < 2; slot++) {
+        const int ch = 2 * d + slot;
+        uint32_t lo = ch == f.r_off ? r_lo : ch == f.b_off ? b_lo : ch == f.g_off ? 6 : 0x0d;
+        uint32_t hi = lo == 0x0d ? 0x0d : lo + 1;
+        if (be) {
+          const uint32_t t = lo;
+          lo = hi;
+          hi = t;
+        }
+        s |= (lo << (16 * slot)) | (hi << (16 * slot + 8));
+      }
+      q.mhc_sel[rk][d] = s;
+    }
+  }
+}
+
 /* Deep samples: the kernel arguments that follow from the cfg (bayer2rgb_deep_kernel, mibayer_kernels.hip).  8-bit
  * output reuses the 8-bit path's selectors (c->sel); 16-bit output pixel k of a pair is two dwords, each a v_perm of
  * {M = [R'_k, B'_k], G pair word}: bytes 4,5 = R', 6,7 = B', 2h,2h+1 = G of pixel parity h, 0x0d = 0xff (alpha),
@@ -751,6 +793,8 @@ static void make_deep_plan (mibayer_ctx *c)
   q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
   q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
   q.out_shift = c->deep_out16 ? 16 - depth : depth - 8;
+  if (c->mhc)
+    make_mhc_selectors (c, depth);
   for (int k = 0; k < 4; k++)
     q.sel[k] = c->sel[k];
   int rp = f.r_off, bp = f.b_off;
@@ -793,7 +837,10 @@ static void make_deep_plan (mibayer_ctx *c)
 static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1)
 {
-  HIP_TRY (launch_deep (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
+  if (c->mhc)
+    HIP_TRY (launch_mhc (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
+  else
+    HIP_TRY (launch_deep (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
   return MIBAYER_OK;
 }
 
@@ -961,7 +1008,7 @@ static int launch (const mibayer_ctx *c, const void *d_src,
 {
   if (nframes == 0 || ntile_rows == 0)
     return MIBAYER_OK;
-  if (c->deep) {                /* tile rows = chunks of kDeepRows rows */
+  if (c->deep) {                /* tile rows = chunks of deep_rows (c) rows */
     DeepParams q = c->deep_args;
     q.src = (const uint8_t *) d_src;
     q.dst = (uint8_t *) d_dst;
@@ -1127,8 +1174,11 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     return MIBAYER_ERR_ARG;
   constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
       | MIBAYER_FLAG_DST_BIG_ENDIAN;
-  if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags))
+  if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags
+          | MIBAYER_FLAG_MHC))
     return MIBAYER_ERR_ARG;
+  if ((f.flags & MIBAYER_FLAG_MHC) && ((f.flags & MIBAYER_FLAG_RGB2BAYER) || f.variant != 0))
+    return MIBAYER_ERR_ARG;                     /* one kernel shape, and no MHC mosaicking */
   const uint32_t src_bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
   if ((f.flags & kDeepFlags) && (f.flags & MIBAYER_FLAG_RGB2BAYER))
     return MIBAYER_ERR_ARG;                     /* high-bit rgb2bayer does not exist */
@@ -1231,7 +1281,8 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->src_bytes = (size_t) f.src_stride * f.height;
   c->dst_bytes = (size_t) f.dst_stride * f.height;
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
-  c->deep = (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
+  c->mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
+  c->deep = c->mhc || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1557,7 +1608,7 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   int rc = validate (cfg, &f);
   if (rc != MIBAYER_OK)
     return rc;
-  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT))
+  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_MHC))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -1589,6 +1640,8 @@ extern "C" int mibayer_known_width_plan (int width, int *variant, int *band)
 
 extern "C" const char *mibayer_ctx_variant_name (const mibayer_ctx *c)
 {
+  if (c && c->mhc)
+    return "mhc_256x16";
   return c ? c->plan[PLAN_BATCH].var->name : NULL;
 }
 
@@ -1756,14 +1809,19 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
 }
 
 /* Host path, one frame cut into horizontal bands: band b's kernel needs source
- * rows y0-1 .. y1 (one halo row above and below), so upload chunk b carries the
- * band's rows plus the row below it, and the chunks run down the frame in one
+ * rows y0-1 .. y1 (one halo row above and below; MHC: y0-2 .. y1+1), so upload chunk b carries the
+ * band's rows plus the halo rows below it, and the chunks run down the frame in one
  * queue.  With the three queues of the ring, the download of band b-1 (4 B/px,
  * the long pole: PCIe is full duplex) overlaps the upload of band b+1 and the
  * kernel of band b inside ONE frame -- the synchronous 1-in/1-out element mode
  * gets most of what the queued mode gets from overlapping whole frames.
  * Bands are whole tile rows; the bottom-edge rule dn(H-1) = H-4
  * (gstbayer2rgb.c:430-447) needs the last band to hold at least 4 rows. */
+static int deep_rows (const mibayer_ctx *c)
+{
+  return c->mhc ? kMhcRows : kDeepRows;
+}
+
 static int choose_host_bands (const mibayer_ctx *c)
 {
   int want = 4;
@@ -1776,7 +1834,7 @@ static int choose_host_bands (const mibayer_ctx *c)
       || big_side < ((size_t) 16 << 20))        /* below ~4K the extra enqueues cost more
                                                    than the overlap gains (1080p: -10 %) */
     return 1;
-  const int th = c->inverse ? kInverseBandUnit : c->deep ? kDeepRows : plan_for (c, 1).var->tile_h;
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? deep_rows (c) : plan_for (c, 1).var->tile_h;
   const int tiles_y = (c->cfg.height + th - 1) / th;
   while (want > 1) {
     const int per = (tiles_y + want - 1) / want;        /* tile rows per band */
@@ -1793,8 +1851,8 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     uint8_t *dst, size_t row_bytes)
 {
   const mibayer_cfg &f = c->cfg;
-  const int th = c->inverse ? kInverseBandUnit : c->deep ? kDeepRows : plan_for (c, 1).var->tile_h;
-  const int halo = c->inverse ? 0 : 1;  /* rgb2bayer has no neighbourhood */
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? deep_rows (c) : plan_for (c, 1).var->tile_h;
+  const int halo = c->inverse ? 0 : c->mhc ? 2 : 1;    /* rgb2bayer has no neighbourhood, MHC's is 5x5 */
   const int tiles_y = (f.height + th - 1) / th;
   const int nb = c->host_bands;
   const int per = (tiles_y + nb - 1) / nb;
@@ -3263,7 +3321,8 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     size_t src_frame_bytes, uint32_t first_frame, int nframes, uint32_t seed,
     void *hip_stream)
 {
-  if (!c || !d_src || nframes < 0 || c->inverse || c->deep)
+  /* the generator writes 8-bit mosaics: an MHC context of one takes it, no other deep context does */
+  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !(c->mhc && c->deep_in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

@@ -250,6 +250,12 @@ struct DeepParams {
   int out_shift;                /* 16-bit out: left shift (16 - bits); 8-bit out: right shift (bits - 8) */
   uint32_t sel[4];              /* 8-bit out: v_perm selectors of output pixel k (mibayer_plan_selectors) */
   uint32_t sel16[2][2];         /* 16-bit out: [pixel parity][dword of the pixel], over {R'B' word, G word} */
+  /* MIBAYER_FLAG_MHC (bayer2rgb_mhc_kernel) */
+  int mhc_green_odd;            /* green sites of row 0 are at odd columns (bggr, rggb) */
+  int mhc_red_odd;              /* red sites are in odd rows (bggr, gbrg) */
+  int mhc_max;                  /* 2^depth - 1 */
+  uint32_t mhc_sel[2][2];       /* [row: 0 = its non-green colour is R, 1 = B][output dword], v_perm selectors over
+                                   {x = [C, G], y = [D, 0]} at output depth; 4-byte output uses [.][0] only */
   /* filled by launch_deep */
   int groups;                   /* 4-pixel groups per row = ceil (width / 4) */
   FastDiv div_tiles_x;          /* 256-pixel strips per row */
@@ -263,6 +269,12 @@ struct DeepParams {
 /* in8: 8-bit mosaic (then out16 is set); out16: 8-byte output pixels.  Chunks [chunk0, chunk0 + nchunks) of the batch
  * (nchunks < 0: all of p.nlist frames, or of `nframes`) */
 hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
+    long long chunk0 = 0, long long nchunks = -1);
+
+/* Malvar-He-Cutler demosaic (MIBAYER_FLAG_MHC) on the deep kernel's arguments: in8 = 8-bit mosaic, out16 = 8-byte
+ * output pixels, all four combinations.  Chunks of kMhcRows rows, otherwise as launch_deep */
+constexpr int kMhcRows = 16;
+hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1);
 
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */

@@ -1714,17 +1714,16 @@ bayer2rgb_deep_kernel (DeepParams p)
   }
 }
 
-hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
-    long long chunk0, long long nchunks)
+/* the launch-dependent fields of q (strips of 256 pixels x `rows`-row chunks, chunks [chunk0, chunk0 + nchunks) of the
+ * batch, nchunks < 0: all) and the grid; *grid = 0: nothing to launch */
+static hipError_t deep_grid (DeepParams &q, int rows, int nframes, long long chunk0, long long nchunks, unsigned *grid)
 {
-  if (p.width < 4 || p.height < 3 || (p.width & 1) || (in8 && !out16))
-    return hipErrorInvalidValue;
-  DeepParams q = p;
-  q.groups = (p.width + 3) / 4;
+  *grid = 0;
+  q.groups = (q.width + 3) / 4;
   const int tiles_x = (q.groups + 63) / 64;
-  const long long chunks_per_frame = (p.height + kDeepRows - 1) / kDeepRows;
-  const long long frames = p.nlist > 0 ? p.nlist : nframes;
-  if (p.nlist > kMaxList || frames <= 0)
+  const long long chunks_per_frame = (q.height + rows - 1) / rows;
+  const long long frames = q.nlist > 0 ? q.nlist : nframes;
+  if (q.nlist > kMaxList || frames <= 0)
     return frames == 0 ? hipSuccess : hipErrorInvalidValue;
   const long long total = frames * chunks_per_frame;
   if (nchunks < 0) {
@@ -1742,13 +1741,256 @@ hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, 
   q.div_chunks = make_fastdiv ((uint32_t) chunks_per_frame);
   q.chunk0 = (uint32_t) chunk0;
   q.nwaves = (uint32_t) waves;
-  const unsigned grid = (unsigned) ((waves + 3) / 4);
+  *grid = (unsigned) ((waves + 3) / 4);
+  return hipSuccess;
+}
+
+hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
+    long long chunk0, long long nchunks)
+{
+  if (p.width < 4 || p.height < 3 || (p.width & 1) || (in8 && !out16))
+    return hipErrorInvalidValue;
+  DeepParams q = p;
+  unsigned grid = 0;
+  const hipError_t e = deep_grid (q, kDeepRows, nframes, chunk0, nchunks, &grid);
+  if (e != hipSuccess || grid == 0)
+    return e;
   if (in8)
     hipLaunchKernelGGL ((bayer2rgb_deep_kernel<true, true>), dim3 (grid), dim3 (256), 0, stream, q);
   else if (out16)
     hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, true>), dim3 (grid), dim3 (256), 0, stream, q);
   else
     hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, false>), dim3 (grid), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
+/* Malvar-He-Cutler demosaic (MIBAYER_FLAG_MHC)                                */
+/* ------------------------------------------------------------------------- */
+/* Gradient-corrected linear interpolation (Malvar, He, Cutler, ICASSP 2004) on a 5x5 stencil, the filters scaled by
+ * 16 to integers, int32 sums, v = clamp ((acc + 8) >> 4, 0, 2^depth - 1), reflect-101 borders (-1 -> 1, -2 -> 2,
+ * W -> W-2, W+1 -> W-3, rows alike).  With c = S(y,x), h1 / h2 = the sums of the samples 1 / 2 columns left and right,
+ * v1 / v2 the same above and below, d = the four diagonal neighbours:
+ *   green at an R / B site      F_G    = 8c + 4(h1 + v1) - 2(h2 + v2)
+ *   the row colour at a G site  F_row  = 10c + 8h1 - 2h2 - 2d + v2
+ *   the column colour there     F_col  = 10c + 8v1 - 2v2 - 2d + h2
+ *   B at R / R at B             F_diag = 12c + 4d - 3(h2 + v2)
+ * Per row the non-green site colour is C (R in a red row, B in a blue one) and the other one D: a non-green site is
+ * C = S, G = F_G, D = F_diag; a green site G = S, C = F_row, D = F_col.  Which of C / D is R is a property of the row,
+ * so it only picks the output selectors (DeepParams::mhc_sel).  Samples and output conversion are the deep path's.
+ *
+ * Shape: the deep kernel's.  A lane owns 4 pixels, a wave a strip of 256 pixels x kMhcRows rows; it loads all
+ * kMhcRows + 4 source rows first, then walks down with a 5-row window of unpacked rows in registers.  Columns x0-2,
+ * x0-1 and x0+4, x0+5 come from the adjacent lanes by DPP (lanes 0 and 63 load their own edge dword), the border
+ * columns are reflected in the lanes that hold them. */
+
+/* one source row as the stencil needs it, pixel k = x0 + k: the sample, the sum of its +-1 neighbours, of its +-2 */
+struct MhcRow { int c[4], h1[4], h2[4]; };
+
+template <bool IN8>
+__device__ __forceinline__ MhcRow mhc_row (const DeepParams &p, const DeepRaw &raw, int lane, bool first, int lastmode)
+{
+  const bool partial = lastmode == 2;
+  uint32_t lo, hi, e;           /* samples as two 16-bit halves: [x0, x0+1], [x0+2, x0+3], the edge pair */
+  if constexpr (IN8) {
+    lo = __builtin_amdgcn_perm (raw.a, raw.a, 0x0c010c00u);
+    hi = __builtin_amdgcn_perm (raw.a, raw.a, 0x0c030c02u);
+    e = __builtin_amdgcn_perm (raw.e, raw.e, lane == 0 ? 0x0c030c02u : 0x0c010c00u);
+  } else {
+    const uint32_t a = partial ? raw.b : raw.a;
+    lo = __builtin_amdgcn_perm (a, a, p.in_sel) & p.mask2;
+    hi = partial ? 0u : __builtin_amdgcn_perm (raw.b, raw.b, p.in_sel) & p.mask2;
+    e = __builtin_amdgcn_perm (raw.e, raw.e, p.in_sel) & p.mask2;
+  }
+  uint32_t q[4];
+  q[0] = from_lane_below (e, hi);                       /* [x0-2, x0-1] */
+  q[1] = lo;
+  q[2] = hi;
+  q[3] = from_lane_above (e, lo);                       /* [x0+4, x0+5] */
+  /* reflect-101 at the borders */
+  if (first)
+    q[0] = bsel (kLowHalves, q[2], q[1]);               /* S(-2) = S(2), S(-1) = S(1) */
+  if (lastmode == 1)
+    q[3] = bsel (kLowHalves, q[2], q[1]);               /* x0 = W-4: S(W) = S(W-2), S(W+1) = S(W-3) */
+  if (partial)
+    q[2] = bsel (kLowHalves, q[1], q[0]);               /* x0 = W-2: S(W) = S(W-2), S(W+1) = S(W-3) */
+  int s[8];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    s[2 * i] = (int) (q[i] & 0xffffu);
+    s[2 * i + 1] = (int) (q[i] >> 16);
+  }
+  MhcRow r;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    r.c[k] = s[k + 2];
+    r.h1[k] = s[k + 1] + s[k + 3];
+    r.h2[k] = s[k] + s[k + 4];
+  }
+  return r;
+}
+
+/* pixel k of the centre row z; returns C, G, D at output depth */
+template <bool GREEN>
+__device__ __forceinline__ void mhc_pixel (const DeepParams &p, const MhcRow &m2, const MhcRow &m1, const MhcRow &z,
+    const MhcRow &p1, const MhcRow &p2, int k, int &C, int &G, int &D)
+{
+  const int c = z.c[k];
+  const int h1 = z.h1[k], h2 = z.h2[k];
+  const int v1 = m1.c[k] + p1.c[k];
+  const int v2 = m2.c[k] + p2.c[k];
+  const int d = m1.h1[k] + p1.h1[k];
+  int f1, f2;
+  if constexpr (GREEN) {
+    G = c;
+    f1 = 10 * c + 8 * h1 - 2 * (h2 + d) + v2;           /* C = F_row */
+    f2 = 10 * c + 8 * v1 - 2 * (v2 + d) + h2;           /* D = F_col */
+  } else {
+    C = c;
+    f1 = 8 * c + 4 * (h1 + v1) - 2 * (h2 + v2);         /* G = F_G */
+    f2 = 12 * c + 4 * d - 3 * (h2 + v2);                /* D = F_diag */
+  }
+  f1 = min (max ((f1 + 8) >> 4, 0), p.mhc_max);      /* v_med3_i32 */
+  f2 = min (max ((f2 + 8) >> 4, 0), p.mhc_max);
+  if constexpr (GREEN)
+    C = f1;
+  else
+    G = f1;
+  D = f2;
+}
+
+template <bool IN8, bool OUT16>
+__global__ void __launch_bounds__ (256)
+bayer2rgb_mhc_kernel (DeepParams p)
+{
+  const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (wave >= p.nwaves)
+    return;
+  const int lane = (int) (threadIdx.x & 63u);
+  const uint32_t crow = fastdiv (wave, p.div_tiles_x);
+  const uint32_t tx = wave - crow * p.div_tiles_x.d;
+  const uint32_t chunk = p.chunk0 + crow;
+  const uint32_t frame = fastdiv (chunk, p.div_chunks);
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kMhcRows;
+  const int y1 = y0 + kMhcRows < p.height ? y0 + kMhcRows : p.height;
+  const uint8_t *src = p.nlist
+      ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
+  uint8_t *dst = p.nlist
+      ? kernarg_table_entry<uint8_t *> (offsetof (DeepParams, dst_list), frame) : p.dst + frame * p.dst_frame_bytes;
+  const int g = (int) tx * 64 + lane;
+  const bool first = g == 0;
+  const int lastmode = g == p.groups - 1 ? ((p.width & 3) ? 2 : 1) : 0;
+  const bool store = g < p.groups;
+  const bool full = 4 * g + 4 <= p.width;
+
+  /* raw[i] = row y0 - 2 + i, reflected; rows past y1 + 1 (a short last chunk) are never used and read row H-1 */
+  DeepRaw raw[kMhcRows + 4];
+#pragma unroll
+  for (int i = 0; i < kMhcRows + 4; i++) {
+    int r = y0 - 2 + i;
+    r = r < 0 ? -r : r;
+    r = r > p.height + 1 ? p.height - 1 : r >= p.height ? 2 * p.height - 2 - r : r;
+    raw[i] = deep_load<IN8> (p, src, r, g, lane);
+  }
+  MhcRow w0 = mhc_row<IN8> (p, raw[0], lane, first, lastmode);
+  MhcRow w1 = mhc_row<IN8> (p, raw[1], lane, first, lastmode);
+  MhcRow w2 = mhc_row<IN8> (p, raw[2], lane, first, lastmode);
+  MhcRow w3 = mhc_row<IN8> (p, raw[3], lane, first, lastmode);
+#pragma unroll
+  for (int k = 0; k < kMhcRows; k++) {
+    const int j = y0 + k;
+    if (j >= y1)
+      break;
+    const MhcRow w4 = mhc_row<IN8> (p, raw[k + 4], lane, first, lastmode);
+    int C[4], G[4], D[4];
+    if (((j & 1) ^ p.mhc_green_odd) == 0) {             /* green at even columns (x0 is even) */
+      mhc_pixel<true> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
+      mhc_pixel<false> (p, w0, w1, w2, w3, w4, 1, C[1], G[1], D[1]);
+      mhc_pixel<true> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
+      mhc_pixel<false> (p, w0, w1, w2, w3, w4, 3, C[3], G[3], D[3]);
+    } else {
+      mhc_pixel<false> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
+      mhc_pixel<true> (p, w0, w1, w2, w3, w4, 1, C[1], G[1], D[1]);
+      mhc_pixel<false> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
+      mhc_pixel<true> (p, w0, w1, w2, w3, w4, 3, C[3], G[3], D[3]);
+    }
+    const int rk = (j & 1) ^ p.mhc_red_odd;             /* 0: C is R (red row), 1: C is B */
+    const int s = p.out_shift;
+    uint32_t x[4], y[4];                                /* x = [C, G], y = [D, 0] at output depth */
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      if constexpr (OUT16) {
+        x[i] = ((uint32_t) C[i] << s) | ((uint32_t) G[i] << (16 + s));
+        y[i] = (uint32_t) D[i] << s;
+      } else {
+        x[i] = ((uint32_t) C[i] >> s) | (((uint32_t) G[i] >> s) << 16);
+        y[i] = (uint32_t) D[i] >> s;
+      }
+    }
+    uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
+    if constexpr (OUT16) {
+      const uint32_t s0 = p.mhc_sel[rk][0], s1 = p.mhc_sel[rk][1];
+      u32x4 v0, v1;
+      v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+      v0.y = __builtin_amdgcn_perm (x[0], y[0], s1);
+      v0.z = __builtin_amdgcn_perm (x[1], y[1], s0);
+      v0.w = __builtin_amdgcn_perm (x[1], y[1], s1);
+      v1.x = __builtin_amdgcn_perm (x[2], y[2], s0);
+      v1.y = __builtin_amdgcn_perm (x[2], y[2], s1);
+      v1.z = __builtin_amdgcn_perm (x[3], y[3], s0);
+      v1.w = __builtin_amdgcn_perm (x[3], y[3], s1);
+      /* the deep kernel's store: the lanes of a quad swap pieces so that each store writes 64 contiguous bytes */
+      const int kq = lane & 3;
+      u32x4 s0v, s1v;
+      deep_quad_pieces (v0, v1, kq, s0v, s1v);
+      const int qg = g - kq;
+      const int ga = qg + (kq >> 1), gb = qg + 2 + (kq >> 1);
+      if (ga < p.groups && ((kq & 1) == 0 || 4 * ga + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * kq) = s0v;
+      if (gb < p.groups && ((kq & 1) == 0 || 4 * gb + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * kq) = s1v;
+    } else {
+      const uint32_t s0 = p.mhc_sel[rk][0];
+      u32x4 v;
+      v.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+      v.y = __builtin_amdgcn_perm (x[1], y[1], s0);
+      v.z = __builtin_amdgcn_perm (x[2], y[2], s0);
+      v.w = __builtin_amdgcn_perm (x[3], y[3], s0);
+      if (store) {
+        uint8_t *q = out + 16 * (size_t) g;
+        if (full) {
+          __builtin_nontemporal_store (v, (u32x4_a4 *) q);
+        } else {
+          const u32x2_a4 two = { v.x, v.y };
+          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+        }
+      }
+    }
+    w0 = w1;
+    w1 = w2;
+    w2 = w3;
+    w3 = w4;
+  }
+}
+
+hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
+    long long chunk0, long long nchunks)
+{
+  if (p.width < 4 || p.height < 3 || (p.width & 1))
+    return hipErrorInvalidValue;
+  DeepParams q = p;
+  unsigned grid = 0;
+  const hipError_t e = deep_grid (q, kMhcRows, nframes, chunk0, nchunks, &grid);
+  if (e != hipSuccess || grid == 0)
+    return e;
+  if (in8 && out16)
+    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<true, true>), dim3 (grid), dim3 (256), 0, stream, q);
+  else if (in8)
+    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<true, false>), dim3 (grid), dim3 (256), 0, stream, q);
+  else if (out16)
+    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<false, true>), dim3 (grid), dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<false, false>), dim3 (grid), dim3 (256), 0, stream, q);
   return hipGetLastError ();
 }
 

@@ -45,8 +45,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "gstmibayer.h"
 #include "gstmibayerelement.h"
 #include "gstmihostpool.h"
+
+#define MI_BAYER_METHOD_TYPE_NAME MIBAYER_TYPE_NAME ("Bayer2RGBMethod")
 
 /* each element logs into its own category, named like the reference's
  * ("bayer2rgb", "rgb2bayer"); the category lives in the class */
@@ -72,7 +75,8 @@ enum
   PROP_INFLIGHT,
   PROP_HIPGRAPH,
   PROP_PINNED_POOL,
-  PROP_TIMEOUT_MS
+  PROP_TIMEOUT_MS,
+  PROP_METHOD
 };
 
 #define DEFAULT_DEVICE_ID 0
@@ -80,6 +84,26 @@ enum
 #define DEFAULT_HIPGRAPH FALSE
 #define DEFAULT_PINNED_POOL TRUE
 #define DEFAULT_TIMEOUT_MS 10000
+#define DEFAULT_METHOD GST_MI_BAYER_METHOD_BILINEAR
+
+/* bayer2rgb's `method`: the reference's bilinear demosaic (bit-exact) or Malvar-He-Cutler (MIBAYER_FLAG_MHC) */
+static GType
+gst_mi_bayer_method_get_type (void)
+{
+  static gsize type = 0;
+  static const GEnumValue values[] = {
+    {GST_MI_BAYER_METHOD_BILINEAR, "Bilinear, bit-exact with the stock element",
+        "bilinear"},
+    {GST_MI_BAYER_METHOD_MHC,
+        "Malvar-He-Cutler gradient-corrected 5x5 interpolation", "mhc"},
+    {0, NULL, NULL}
+  };
+  if (g_once_init_enter (&type)) {
+    GType t = g_enum_register_static (MI_BAYER_METHOD_TYPE_NAME, values);
+    g_once_init_leave (&type, t);
+  }
+  return (GType) type;
+}
 
 /* one frame between submit and wait: both buffers stay mapped until the GPU
  * has written the output */
@@ -451,7 +475,8 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       | (inverse ? MIBAYER_FLAG_RGB2BAYER : 0)
       | MIBAYER_FLAG_SRC_BITS (self->src_bits)
       | (self->src_big_endian ? MIBAYER_FLAG_SRC_BIG_ENDIAN : 0)
-      | (self->out16 ? MIBAYER_FLAG_DST_16BIT : 0);
+      | (self->out16 ? MIBAYER_FLAG_DST_16BIT : 0)
+      | (!inverse && self->act.method == GST_MI_BAYER_METHOD_MHC ? MIBAYER_FLAG_MHC : 0);
   if (!element_parse_devices (self, &pc)) {
     element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
         g_strdup_printf ("%s: cannot parse devices=\"%s\"", LABEL (self),
@@ -529,6 +554,9 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
     case PROP_TIMEOUT_MS:
       self->timeout_ms = g_value_get_int (value);
       break;
+    case PROP_METHOD:
+      self->method = g_value_get_enum (value);
+      break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
       break;
@@ -561,6 +589,9 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
       break;
     case PROP_TIMEOUT_MS:
       g_value_set_int (value, self->timeout_ms);
+      break;
+    case PROP_METHOD:
+      g_value_set_enum (value, self->method);
       break;
     default:
       G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
@@ -1130,6 +1161,7 @@ element_start (GstBaseTransform * base)
   self->act.use_hipgraph = self->use_hipgraph;
   self->act.pinned_pool = self->pinned_pool;
   self->act.timeout_ms = self->timeout_ms;
+  self->act.method = self->method;
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
   self->prerolled = FALSE;
@@ -1203,6 +1235,15 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
           "out instead of hanging); 0 = wait for ever (latched when the element "
           "starts)", 0, 3600000, DEFAULT_TIMEOUT_MS,
           G_PARAM_READWRITE | G_PARAM_STATIC_STRINGS));
+  if (!inverse)
+    g_object_class_install_property (object_class, PROP_METHOD,
+        g_param_spec_enum ("method", "Demosaic method",
+            "bilinear: the stock element's algorithm, bit-exact; mhc: "
+            "Malvar-He-Cutler gradient-corrected interpolation (fewer zipper "
+            "and colour-fringe artefacts on edges, not bit-exact with the "
+            "stock element)", gst_mi_bayer_method_get_type (), DEFAULT_METHOD,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
   transform_class->get_unit_size = GST_DEBUG_FUNCPTR (element_get_unit_size);
@@ -1231,6 +1272,8 @@ gst_mi_bayer_element_instance_setup (GstMiBayerElement * self)
   self->pinned_pool = DEFAULT_PINNED_POOL;
   self->timeout_ms = DEFAULT_TIMEOUT_MS;
   self->act.timeout_ms = DEFAULT_TIMEOUT_MS;
+  self->method = DEFAULT_METHOD;
+  self->act.method = DEFAULT_METHOD;
   self->error_text = self->error_debug = NULL;
   self->act.device_id = DEFAULT_DEVICE_ID;
   self->act.devices = NULL;

@@ -19,6 +19,13 @@
 
 G_BEGIN_DECLS
 
+/* bayer2rgb's `method` property */
+typedef enum
+{
+  GST_MI_BAYER_METHOD_BILINEAR = 0,     /* the reference's algorithm, bit-exact */
+  GST_MI_BAYER_METHOD_MHC = 1           /* Malvar-He-Cutler (MIBAYER_FLAG_MHC) */
+} GstMiBayerMethod;
+
 typedef struct _GstMiBayerElement GstMiBayerElement;
 typedef struct _GstMiBayerElementClass GstMiBayerElementClass;
 
@@ -52,6 +59,7 @@ struct _GstMiBayerElement
   gboolean use_hipgraph;
   gboolean pinned_pool;
   gint timeout_ms;              /* deadline of every wait for a GPU; 0 = none */
+  gint method;                  /* GstMiBayerMethod (bayer2rgb only) */
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -63,6 +71,7 @@ struct _GstMiBayerElement
     gboolean use_hipgraph;
     gboolean pinned_pool;
     gint timeout_ms;
+    gint method;
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;

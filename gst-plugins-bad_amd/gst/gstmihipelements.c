@@ -44,8 +44,31 @@ enum
   PROP_BATCH,
   PROP_AUTOTUNE,
   PROP_PLAN,
-  PROP_OVERLAP
+  PROP_OVERLAP,
+  PROP_METHOD
 };
+
+/* hipbayer2rgb's `method` (values as bayer2rgb's): the reference's bilinear demosaic or Malvar-He-Cutler */
+#define HB2R_METHOD_BILINEAR 0
+#define HB2R_METHOD_MHC 1
+
+static GType
+hb2r_method_get_type (void)
+{
+  static gsize type = 0;
+  static const GEnumValue values[] = {
+    {HB2R_METHOD_BILINEAR, "Bilinear, bit-exact with the stock bayer2rgb",
+        "bilinear"},
+    {HB2R_METHOD_MHC, "Malvar-He-Cutler gradient-corrected 5x5 interpolation",
+        "mhc"},
+    {0, NULL, NULL}
+  };
+  if (g_once_init_enter (&type)) {
+    GType t = g_enum_register_static ("GstMiHipBayer2RGBMethod", values);
+    g_once_init_leave (&type, t);
+  }
+  return (GType) type;
+}
 
 /* bytes of one frame for either media type; same rules as bayer2rgb's
  * get_unit_size (reference gstbayer2rgb.c:324-352) for the two it knows */
@@ -795,6 +818,8 @@ typedef struct
   gint launch_ev_device;
   guint busy_run;               /* consecutive frames that arrived while the previous conversion was still running */
   gchar plan[160];              /* property "plan" (read-only): the context's launch plan and where it came from */
+  gint method;                  /* property "method" (HB2R_METHOD_*; g_atomic_int_*), read when a context is made */
+  gboolean ctx_mhc;             /* the context runs the MHC kernel: one kernel shape, no plan to measure */
   gboolean prerolled;           /* a frame has left since start / flush: batching may begin */
   GQueue waiting;               /* Hb2rPair* */
   GQueue ready;                 /* GstBuffer* */
@@ -896,6 +921,9 @@ hb2r_set_property (GObject * object, guint prop_id, const GValue * value,
   else if (prop_id == PROP_OVERLAP)
     g_atomic_int_set (&((GstMiHipBayer2RGB *) object)->overlap,
         g_value_get_boolean (value) ? 1 : 0);
+  else if (prop_id == PROP_METHOD)
+    g_atomic_int_set (&((GstMiHipBayer2RGB *) object)->method,
+        g_value_get_enum (value));
   else
     G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
 }
@@ -915,6 +943,9 @@ hb2r_get_property (GObject * object, guint prop_id, GValue * value,
   else if (prop_id == PROP_OVERLAP)
     g_value_set_boolean (value,
         g_atomic_int_get (&((GstMiHipBayer2RGB *) object)->overlap) != 0);
+  else if (prop_id == PROP_METHOD)
+    g_value_set_enum (value,
+        g_atomic_int_get (&((GstMiHipBayer2RGB *) object)->method));
   else if (prop_id == PROP_PLAN) {
     GST_OBJECT_LOCK (object);
     g_value_set_string (value, ((GstMiHipBayer2RGB *) object)->plan);
@@ -1075,6 +1106,13 @@ hb2r_note_plan (GstMiHipBayer2RGB * self)
   int variant = 0, band = 0, align = 0, src = -1;
   const char *name;
 
+  if (self->ctx_mhc) {          /* one kernel shape, nothing to choose */
+    GST_OBJECT_LOCK (self);
+    g_snprintf (self->plan, sizeof self->plan, "%s source=default", mibayer_ctx_variant_name (self->ctx));
+    GST_OBJECT_UNLOCK (self);
+    GST_INFO_OBJECT (self, "launch plan: %s", self->plan);
+    return;
+  }
   /* the plan of the launches this element issues: `batch` frames each (ABI v5: one plan per launch class) */
   (void) mibayer_get_plan_for (self->ctx, hb2r_launch_frames (self), &variant, &band, &align, &src);
   name = mibayer_variant_name (variant);
@@ -1105,6 +1143,9 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
   cfg.b_off = self->b_off;
   cfg.device = device;
   cfg.flags = HB2R_INVERSE (self) ? MIBAYER_FLAG_RGB2BAYER : 0;
+  self->ctx_mhc = !HB2R_INVERSE (self) && g_atomic_int_get (&self->method) == HB2R_METHOD_MHC;
+  if (self->ctx_mhc)
+    cfg.flags |= MIBAYER_FLAG_MHC;
   rc = mibayer_create (&cfg, &self->ctx);
   if (rc != MIBAYER_OK) {
     self->ctx = NULL;
@@ -1139,8 +1180,8 @@ hb2r_autotune_once (GstMiHipBayer2RGB * self, const void *const *srcs,
   if (self->tuned)
     return;
   self->tuned = TRUE;           /* from here on the launches may leave the context's stream (hb2r_next_stream) */
-  if (HB2R_INVERSE (self))
-    return;                     /* rgb2bayer has one launch shape: nothing to measure */
+  if (HB2R_INVERSE (self) || self->ctx_mhc)
+    return;                     /* rgb2bayer and MHC have one launch shape: nothing to measure */
   (void) mibayer_get_plan_for (self->ctx, (int) n, NULL, NULL, NULL, &src);
   if (src != MIBAYER_PLAN_DEFAULT)
     return;                     /* the process cache had a plan for this launch class when the context was created */
@@ -1613,6 +1654,14 @@ gst_mi_hip_bayer2rgb_class_init (GstMiHipBayer2RGBClass * klass)
           "The launch plan of the current stream and where it came from "
           "(default / measured / cached)", "",
           G_PARAM_READABLE | G_PARAM_STATIC_STRINGS));
+  g_object_class_install_property (object_class, PROP_METHOD,
+      g_param_spec_enum ("method", "Demosaic method",
+          "bilinear: the stock bayer2rgb's algorithm, bit-exact; mhc: "
+          "Malvar-He-Cutler gradient-corrected interpolation (fewer zipper and "
+          "colour-fringe artefacts on edges, not bit-exact with the stock "
+          "element; autotune has nothing to measure).  No effect on hiprgb2bayer",
+          hb2r_method_get_type (), HB2R_METHOD_BILINEAR,
+          G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY | G_PARAM_STATIC_STRINGS));
   xfer_add_templates (element_class, HB2R_SINK_CAPS, HB2R_SRC_CAPS);
   gst_element_class_set_static_metadata (element_class,
       "Bayer to RGB decoder (HIP device memory)", "Filter/Converter/Video",
@@ -1649,6 +1698,8 @@ gst_mi_hip_bayer2rgb_init (GstMiHipBayer2RGB * self)
   self->busy_run = 0;
   self->tuned = FALSE;
   self->plan[0] = '\0';
+  self->method = HB2R_METHOD_BILINEAR;
+  self->ctx_mhc = FALSE;
   self->prerolled = FALSE;
   g_queue_init (&self->waiting);
   g_queue_init (&self->ready);

@@ -63,7 +63,7 @@ extern "C" {
  * mibayer_set_plan / mibayer_copy_plan pin every class. */
 /* 5, later additive: deep samples -- flags only (MIBAYER_FLAG_SRC_BITS, _SRC_BIG_ENDIAN, _DST_16BIT,
  * _DST_BIG_ENDIAN: 10-16-bit mosaics in 16-bit words, 16-bit-per-channel output); no struct field and no entry point
- * was added, and a cfg without them means what it meant. */
+ * was added, and a cfg without them means what it meant.  Likewise MIBAYER_FLAG_MHC (Malvar-He-Cutler demosaic). */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -202,6 +202,25 @@ typedef struct mibayer_cfg {
 #define MIBAYER_FLAG_SRC_BIG_ENDIAN (1u << 13)
 #define MIBAYER_FLAG_DST_16BIT (1u << 14)
 #define MIBAYER_FLAG_DST_BIG_ENDIAN (1u << 15)
+
+/* Malvar-He-Cutler demosaic (additive within version 5: a flag only).  Instead of the reference's bilinear average, the
+ * gradient-corrected linear interpolation of Malvar, He and Cutler (ICASSP 2004): fewer zipper artefacts and colour
+ * fringes on edges, NOT bit-exact with gst-plugins-bad.  S = the sample as the deep path reads it (8-bit byte, or the
+ * word in its byte order masked to `bits`), depth = 8 or `bits`.  Borders reflect-101 (index -1 -> 1, -2 -> 2,
+ * W -> W-2, W+1 -> W-3, rows alike).  The filters, x16 so that they are integers, by offset (dy,dx):
+ *   F_G    green at an R / B site:          (0,0) 8; (0,+-1),(+-1,0) 4; (0,+-2),(+-2,0) -2
+ *   F_row  the colour left/right of a G:    (0,0) 10; (0,+-1) 8; (0,+-2) -2; (+-1,+-1) -2; (+-2,0) +1
+ *   F_col  the colour above/below a G:      F_row transposed
+ *   F_diag R at a B site / B at an R site:  (0,0) 12; (+-1,+-1) 4; (0,+-2),(+-2,0) -3
+ * R site: R = S, G = F_G, B = F_diag; B site: B = S, G = F_G, R = F_diag; G site: G = S and F_row / F_col for the
+ * colours of its row / column.  v = clamp ((acc + 8) >> 4, 0, 2^depth - 1) on int32 sums, then the deep path's output
+ * conversion and layouts.  Goes with any of the deep flags above and with MIBAYER_FLAG_HIPGRAPH (the host path runs
+ * without graphs); with MIBAYER_FLAG_RGB2BAYER or variant != 0 it is MIBAYER_ERR_ARG.  Strides and their defaults are
+ * those of the same cfg without the flag.  Every host / device / list / pool entry point works on an MHC context;
+ * mibayer_autotune[_list], mibayer_set_plan[_for], mibayer_plan_selectors and mibayer_launch_geometry return
+ * MIBAYER_ERR_ARG (one kernel shape, no plans); mibayer_fill_synthetic works when the mosaic is 8-bit;
+ * mibayer_ctx_variant_name names the MHC kernel. */
+#define MIBAYER_FLAG_MHC (1u << 16)
 
 typedef struct mibayer_ctx mibayer_ctx;
 
