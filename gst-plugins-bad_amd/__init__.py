@@ -86,6 +86,8 @@ FLAG_DST_16BIT = 1 << 14
 FLAG_DST_BIG_ENDIAN = 1 << 15
 FLAG_MHC = 1 << 16              # Malvar-He-Cutler demosaic instead of the reference's bilinear one
 METHODS = {"bilinear": 0, "mhc": FLAG_MHC}      # the `method` keyword of make_cfg / Context / Pool
+FLAG_COLOUR = 1 << 19           # fused colour stage: black level, Q12 matrix, tone curve (struct mibayer_colour)
+TONE_LINEAR, TONE_SRGB, TONE_GAMMA = 0, 1, 2
 
 
 def FLAG_SRC_BITS(n):
@@ -107,6 +109,46 @@ class HostStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Colour(ctypes.Structure):
+    """struct mibayer_colour (include/mibayer.h): the parameters of a FLAG_COLOUR context.  Colour() is the identity;
+    Colour.make() builds one with the library's helpers (mibayer_colour_matrix / mibayer_colour_tone)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("black", ctypes.c_int32 * 3), ("matrix", ctypes.c_int32 * 9),
+                ("has_tone", ctypes.c_int32), ("tone", ctypes.c_uint32 * 257)]
+
+    def __init__(self, black=(0, 0, 0), matrix=(4096, 0, 0, 0, 4096, 0, 0, 0, 4096), tone=None):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(Colour)
+        self.black[:] = [int(v) for v in (black if np.ndim(black) else (black,) * 3)]
+        self.matrix[:] = [int(v) for v in np.asarray(matrix).reshape(-1)]
+        self.has_tone = 0 if tone is None else 1
+        if tone is not None:
+            self.tone[:] = [int(v) for v in tone]
+
+    @classmethod
+    def make(cls, black=0, gains=(1.0, 1.0, 1.0), ccm=None, curve=None, gamma=2.2):
+        """curve: None (no tone curve) or TONE_LINEAR / TONE_SRGB / TONE_GAMMA"""
+        return cls(black, colour_matrix(gains, ccm), None if curve is None else colour_tone(curve, gamma))
+
+    def tone_table(self):
+        return np.array(self.tone[:], np.int64) if self.has_tone else None
+
+
+def colour_matrix(gains=(1.0, 1.0, 1.0), ccm=None):
+    """mibayer_colour_matrix: round(ccm x diag(gains) x 4096) as 9 ints (no device needed)"""
+    out = (ctypes.c_int32 * 9)()
+    g = (ctypes.c_double * 3)(*[float(v) for v in gains])
+    c = None if ccm is None else (ctypes.c_double * 9)(*[float(v) for v in np.asarray(ccm).reshape(-1)])
+    _check(lib().mibayer_colour_matrix(g, c, out), "mibayer_colour_matrix")
+    return list(out)
+
+
+def colour_tone(curve, gamma=2.2):
+    """mibayer_colour_tone: the 257-entry table of TONE_LINEAR / TONE_SRGB / TONE_GAMMA (no device needed)"""
+    out = (ctypes.c_uint32 * 257)()
+    _check(lib().mibayer_colour_tone(int(curve), float(gamma), out), "mibayer_colour_tone")
+    return list(out)
 
 
 class PoolCfg(ctypes.Structure):
@@ -216,6 +258,13 @@ ABI = {
                                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
                                                ctypes.POINTER(ctypes.c_int64)]),
     "mibayer_block_to_tile": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    "mibayer_colour_init": (None, [ctypes.POINTER(Colour)]),
+    "mibayer_set_colour": (ctypes.c_int, [_vp, ctypes.POINTER(Colour)]),
+    "mibayer_get_colour": (ctypes.c_int, [_vp, ctypes.POINTER(Colour)]),
+    "mibayer_pool_set_colour": (ctypes.c_int, [_vp, ctypes.POINTER(Colour)]),
+    "mibayer_colour_matrix": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "mibayer_colour_tone": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 
@@ -286,9 +335,12 @@ def _ptr(a):
 
 def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0, device=-1,
              inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False,
-             method="bilinear"):
+             method="bilinear", colour=None):
     """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
-    name implies out16.  method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC)"""
+    name implies out16.  method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
+    colour: None / False = no colour stage; True or a Colour = FLAG_COLOUR (Context / Pool apply the Colour)"""
+    if colour is not None and colour is not False:
+        flags |= FLAG_COLOUR
     if method not in METHODS:
         raise ValueError("method must be one of %s, not %r" % (sorted(METHODS), method))
     flags |= METHODS[method]
@@ -307,7 +359,7 @@ class Pool:
     """Round-robin frame sharding over HIP devices (mibayer_pool): frame g -> devices[g % N]."""
 
     def __init__(self, devices, width, height, pattern="bggr", fmt="RGBx", inflight=2, flags=0, **deep):
-        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= (make_cfg)"""
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= / colour= (make_cfg)"""
         pc = PoolCfg()
         pc.struct_size = ctypes.sizeof(PoolCfg)
         pc.stream = make_cfg(width, height, pattern, fmt, inflight=inflight, flags=flags, **deep)
@@ -317,6 +369,12 @@ class Pool:
         self._h = _vp()
         _check(lib().mibayer_pool_create(ctypes.byref(pc), ctypes.byref(self._h)), "mibayer_pool_create")
         self.capacity = lib().mibayer_pool_capacity(self._h)
+        if isinstance(deep.get("colour"), Colour):
+            self.set_colour(deep["colour"])
+
+    def set_colour(self, colour):
+        """mibayer_pool_set_colour: the colour stage of every shard, for the frames submitted from now on"""
+        _check(lib().mibayer_pool_set_colour(self._h, ctypes.byref(colour)), "mibayer_pool_set_colour")
 
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_pool_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_pool_submit")
@@ -398,8 +456,8 @@ class Context:
 
     def __init__(self, width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride=0,
                  device=-1, inflight=0, variant=0, flags=0, **deep):
-        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= (make_cfg); a deep context takes its
-        source as bytes or as any integer array whose bytes are the frame (uint16 words)"""
+        """deep: bits= / src_big_endian= / out16= / dst_big_endian= / method= / colour= (make_cfg); a deep context takes
+        its source as bytes or as any integer array whose bytes are the frame (uint16 words)"""
         cfg = make_cfg(width, height, pattern, fmt, src_stride, dst_stride, device, inflight, variant, flags, **deep)
         self._h = _vp()
         _check(lib().mibayer_create(ctypes.byref(cfg), ctypes.byref(self._h)), "mibayer_create")
@@ -413,6 +471,18 @@ class Context:
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
         self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT))
         self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
+        self.colour = bool(out.flags & FLAG_COLOUR)
+        if isinstance(deep.get("colour"), Colour):
+            self.set_colour(deep["colour"])
+
+    def set_colour(self, colour):
+        """mibayer_set_colour: applies to the launches enqueued from now on"""
+        _check(lib().mibayer_set_colour(self._h, ctypes.byref(colour)), "mibayer_set_colour")
+
+    def get_colour(self):
+        out = Colour()
+        _check(lib().mibayer_get_colour(self._h, ctypes.byref(out)), "mibayer_get_colour")
+        return out
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):

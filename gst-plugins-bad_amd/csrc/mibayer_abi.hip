@@ -19,6 +19,7 @@
 
 #include <atomic>
 #include <limits.h>
+#include <math.h>
 #include <mutex>
 #include <new>
 #include <stdio.h>
@@ -158,6 +159,9 @@ struct Slot {
   hipGraphExec_t cexec = nullptr;
   bool cgraph_events = false;     /* the graph holds the event nodes too */
   unsigned plan_epoch = 0;        /* mibayer_ctx::plan_epoch both graphs were built under */
+  /* MIBAYER_FLAG_COLOUR: the stage of the frame in the slot, taken ONCE when the frame is accepted -- every band of
+   * the frame launches with it, whatever mibayer_set_colour does meanwhile */
+  ColourStage stage;
 };
 
 int device_count_cached ()
@@ -294,6 +298,13 @@ struct mibayer_ctx {
   bool deep_in8 = false;                /* 8-bit mosaic (16-bit output unless mhc) */
   bool mhc = false;                     /* MIBAYER_FLAG_MHC: bayer2rgb_mhc_kernel; a deep context, 8-bit ones included */
   bool deep_out16 = false;
+  /* MIBAYER_FLAG_COLOUR: bayer2rgb_colour_kernel, a deep context (8-bit ones included).  A host-path frame takes ONE
+   * copy of the stage under the lock when it is accepted (Slot::stage), a device-path call one per call; the copy
+   * travels in the kernel arguments, so mibayer_set_colour never touches what is already queued */
+  bool colour = false;
+  mutable std::mutex colour_mu;
+  mibayer_colour colour_user;           /* as set (mibayer_get_colour) */
+  ColourStage colour_stage;             /* as the kernel takes it */
   DeepParams deep_args;                 /* the launch-independent fields, made at create */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
@@ -793,7 +804,7 @@ static void make_deep_plan (mibayer_ctx *c)
   q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
   q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
   q.out_shift = c->deep_out16 ? 16 - depth : depth - 8;
-  if (c->mhc)
+  if (c->mhc || c->colour)
     make_mhc_selectors (c, depth);
   for (int k = 0; k < 4; k++)
     q.sel[k] = c->sel[k];
@@ -834,10 +845,24 @@ static void make_deep_plan (mibayer_ctx *c)
 
 /* one launch of the deep kernel: frames at q.src / q.dst + f * frame bytes or the q.nlist frames of q.src_list /
  * q.dst_list, all of them or chunks [chunk0, chunk0 + nchunks) of kDeepRows rows (host-path bands) */
-static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes, hipStream_t stream,
-    long long chunk0 = 0, long long nchunks = -1)
+static void colour_snapshot (const mibayer_ctx *c, ColourStage *st)
 {
-  if (c->mhc)
+  std::lock_guard<std::mutex> lk (c->colour_mu);
+  *st = c->colour_stage;
+}
+
+/* stage: the colour stage to launch with (a colour context); NULL = the context's current one */
+static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes, hipStream_t stream,
+    long long chunk0 = 0, long long nchunks = -1, const ColourStage *stage = nullptr)
+{
+  if (c->colour) {
+    ColourStage now;
+    if (!stage) {
+      colour_snapshot (c, &now);
+      stage = &now;
+    }
+    HIP_TRY (launch_colour (q, *stage, c->mhc, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
+  } else if (c->mhc)
     HIP_TRY (launch_mhc (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
   else
     HIP_TRY (launch_deep (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
@@ -1004,7 +1029,7 @@ static int plan_launch (const mibayer_ctx *c, const void *d_src,
 
 static int launch (const mibayer_ctx *c, const void *d_src,
     size_t src_frame_bytes, void *d_dst, size_t dst_frame_bytes, int nframes,
-    hipStream_t stream, long long tile_row0 = 0, long long ntile_rows = -1)
+    hipStream_t stream, long long tile_row0 = 0, long long ntile_rows = -1, const ColourStage *stage = nullptr)
 {
   if (nframes == 0 || ntile_rows == 0)
     return MIBAYER_OK;
@@ -1015,8 +1040,8 @@ static int launch (const mibayer_ctx *c, const void *d_src,
     q.src_frame_bytes = src_frame_bytes;
     q.dst_frame_bytes = dst_frame_bytes;
     q.nlist = 0;
-    return ntile_rows >= 0 ? launch_deep_kernel (c, q, nframes, stream, tile_row0, ntile_rows)
-        : launch_deep_kernel (c, q, nframes, stream);
+    return ntile_rows >= 0 ? launch_deep_kernel (c, q, nframes, stream, tile_row0, ntile_rows, stage)
+        : launch_deep_kernel (c, q, nframes, stream, 0, -1, stage);
   }
   if (c->inverse) {
     const mibayer_cfg &f = c->cfg;
@@ -1175,9 +1200,9 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
       | MIBAYER_FLAG_DST_BIG_ENDIAN;
   if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags
-          | MIBAYER_FLAG_MHC))
+          | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
-  if ((f.flags & MIBAYER_FLAG_MHC) && ((f.flags & MIBAYER_FLAG_RGB2BAYER) || f.variant != 0))
+  if ((f.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR)) && ((f.flags & MIBAYER_FLAG_RGB2BAYER) || f.variant != 0))
     return MIBAYER_ERR_ARG;                     /* one kernel shape, and no MHC mosaicking */
   const uint32_t src_bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
   if ((f.flags & kDeepFlags) && (f.flags & MIBAYER_FLAG_RGB2BAYER))
@@ -1247,6 +1272,93 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   return MIBAYER_OK;
 }
 
+/* ---- colour stage (MIBAYER_FLAG_COLOUR) ----------------------------------------- */
+
+extern "C" void mibayer_colour_init (mibayer_colour *col)
+{
+  if (!col)
+    return;
+  memset (col, 0, sizeof *col);
+  col->struct_size = sizeof *col;
+  col->matrix[0] = col->matrix[4] = col->matrix[8] = 4096;
+}
+
+/* range checks of mibayer_set_colour, and the matrix split the kernel multiplies with (mibayer_internal.h) */
+static int colour_stage_from (const mibayer_colour *col, ColourStage *st)
+{
+  if (!mibayer_colour_in_range (col))
+    return MIBAYER_ERR_ARG;
+  st->has_tone = col->has_tone;
+  for (int k = 0; k < 3; k++)
+    st->black[k] = col->black[k];
+  for (int k = 0; k < 9; k++) {
+    st->m_hi[k] = col->matrix[k] >> 12;         /* arithmetic: floor */
+    st->m_lo[k] = col->matrix[k] & 4095;
+  }
+  memcpy (st->tone, col->tone, sizeof st->tone);
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_set_colour (mibayer_ctx *c, const mibayer_colour *col)
+{
+  if (!c || !c->colour)
+    return MIBAYER_ERR_ARG;
+  ColourStage st;
+  const int rc = colour_stage_from (col, &st);
+  if (rc != MIBAYER_OK)
+    return rc;
+  std::lock_guard<std::mutex> lk (c->colour_mu);
+  c->colour_user = *col;
+  c->colour_stage = st;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_get_colour (const mibayer_ctx *c, mibayer_colour *out)
+{
+  if (!c || !c->colour || !out)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->colour_mu);
+  *out = c->colour_user;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_colour_matrix (const double gains[3], const double ccm[9], int32_t out[9])
+{
+  if (!gains || !out)
+    return MIBAYER_ERR_ARG;
+  int32_t m[9];
+  for (int k = 0; k < 9; k++) {
+    const double e = (ccm ? ccm[k] : (k % 4 == 0 ? 1.0 : 0.0)) * gains[k % 3] * 4096.0;
+    if (!(e >= -65535.5 && e <= 65535.5))       /* NaN fails both */
+      return MIBAYER_ERR_ARG;
+    const long long r = llround (e);
+    if (r < -65535 || r > 65535)
+      return MIBAYER_ERR_ARG;
+    m[k] = (int32_t) r;
+  }
+  memcpy (out, m, sizeof m);
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_colour_tone (int curve, double gamma, uint32_t tone[257])
+{
+  if (!tone || curve < MIBAYER_TONE_LINEAR || curve > MIBAYER_TONE_GAMMA)
+    return MIBAYER_ERR_ARG;
+  if (curve == MIBAYER_TONE_GAMMA && !(gamma >= 0.01 && gamma <= 100.0))
+    return MIBAYER_ERR_ARG;
+  for (int i = 0; i <= 256; i++) {
+    const double x = i / 256.0;
+    double y = x;
+    if (curve == MIBAYER_TONE_SRGB)
+      y = x <= 0.0031308 ? 12.92 * x : 1.055 * pow (x, 1.0 / 2.4) - 0.055;
+    else if (curve == MIBAYER_TONE_GAMMA)
+      y = pow (x, 1.0 / gamma);
+    const long long v = curve == MIBAYER_TONE_LINEAR ? 256LL * i : llround (y * 65536.0);
+    tone[i] = (uint32_t) (v < 0 ? 0 : v > 65536 ? 65536 : v);
+  }
+  return MIBAYER_OK;
+}
+
 static int choose_host_bands (const mibayer_ctx *c);
 static bool plan_cache_load (mibayer_ctx *c);
 extern "C" void mibayer_internal_private_queues (mibayer_ctx *c);
@@ -1282,7 +1394,12 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->dst_bytes = (size_t) f.dst_stride * f.height;
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
   c->mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
-  c->deep = c->mhc || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
+  c->colour = (f.flags & MIBAYER_FLAG_COLOUR) != 0;
+  if (c->colour) {
+    mibayer_colour_init (&c->colour_user);
+    (void) colour_stage_from (&c->colour_user, &c->colour_stage);
+  }
+  c->deep = c->mhc || c->colour || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1608,7 +1725,8 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   int rc = validate (cfg, &f);
   if (rc != MIBAYER_OK)
     return rc;
-  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_MHC))
+  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_MHC
+          | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -1640,6 +1758,8 @@ extern "C" int mibayer_known_width_plan (int width, int *variant, int *band)
 
 extern "C" const char *mibayer_ctx_variant_name (const mibayer_ctx *c)
 {
+  if (c && c->colour)
+    return c->mhc ? "colour_mhc_256x16" : "colour_bilinear_256x16";
   if (c && c->mhc)
     return "mhc_256x16";
   return c ? c->plan[PLAN_BATCH].var->name : NULL;
@@ -1819,7 +1939,7 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
  * (gstbayer2rgb.c:430-447) needs the last band to hold at least 4 rows. */
 static int deep_rows (const mibayer_ctx *c)
 {
-  return c->mhc ? kMhcRows : kDeepRows;
+  return c->mhc || c->colour ? kMhcRows : kDeepRows;
 }
 
 static int choose_host_bands (const mibayer_ctx *c)
@@ -1852,7 +1972,8 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
 {
   const mibayer_cfg &f = c->cfg;
   const int th = c->inverse ? kInverseBandUnit : c->deep ? deep_rows (c) : plan_for (c, 1).var->tile_h;
-  const int halo = c->inverse ? 0 : c->mhc ? 2 : 1;    /* rgb2bayer has no neighbourhood, MHC's is 5x5 */
+  /* rgb2bayer has no neighbourhood, MHC's is 5x5, and the colour kernel loads the MHC window whatever the method */
+  const int halo = c->inverse ? 0 : c->mhc || c->colour ? 2 : 1;
   const int tiles_y = (f.height + th - 1) / th;
   const int nb = c->host_bands;
   const int per = (tiles_y + nb - 1) / nb;
@@ -1881,7 +2002,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     HIP_TRY (hipEventRecord (s.ev_band_in[b], c->s_h2d));
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_band_in[b], 0));
     int rc = launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1,
-        c->s_compute, t0, t1 - t0);
+        c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
     HIP_TRY (hipEventRecord (s.ev_band_kernel[b], c->s_compute));
@@ -1992,7 +2113,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
     Range r ("mibayer:kernel");
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_in, 0));
     const int rc = launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1,
-        c->s_compute);
+        c->s_compute, 0, -1, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
     HIP_TRY (hipEventRecord (s.ev_kernel, c->s_compute));
@@ -2028,6 +2149,8 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   if (c->pending == (int) c->ring.size ())
     return MIBAYER_ERR_BUSY;
   Slot &s = c->ring[(size_t) c->head];
+  if (c->colour)
+    colour_snapshot (c, &s.stage);      /* one stage per frame, however many bands it is launched in */
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
   const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep;
   if (want_graph && c->graph_mode == 1
@@ -2171,6 +2294,8 @@ extern "C" int mibayer_internal_run_spare (mibayer_ctx *c, const uint8_t *src,
   }
   if (wedged_for_good (c))
     return MIBAYER_ERR_TIMEOUT;
+  if (c->colour)
+    colour_snapshot (c, &c->spare.stage);
   int rc = enqueue_plain (c, c->spare, src, dst, written_row_bytes (c));
   if (rc != MIBAYER_OK) {
     /* nothing of a half-queued frame may touch the buffers after the error */
@@ -2360,6 +2485,9 @@ extern "C" int mibayer_process_device_list (mibayer_ctx *c,
   Range r ("mibayer:process_device_list");
   mark_dirty (c, (hipStream_t) hip_stream);
   if (c->deep) {
+    ColourStage stage;          /* one per call: every launch of a list of more than kMaxList frames takes the same */
+    if (c->colour)
+      colour_snapshot (c, &stage);
     for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
       DeepParams q = c->deep_args;
       q.src = nullptr;
@@ -2369,7 +2497,7 @@ extern "C" int mibayer_process_device_list (mibayer_ctx *c,
         q.src_list[k] = (const uint8_t *) d_srcs[f0 + k];
         q.dst_list[k] = (uint8_t *) d_dsts[f0 + k];
       }
-      const int rc = launch_deep_kernel (c, q, q.nlist, (hipStream_t) hip_stream);
+      const int rc = launch_deep_kernel (c, q, q.nlist, (hipStream_t) hip_stream, 0, -1, c->colour ? &stage : nullptr);
       if (rc != MIBAYER_OK)
         return rc;
     }
@@ -3322,7 +3450,7 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     void *hip_stream)
 {
   /* the generator writes 8-bit mosaics: an MHC context of one takes it, no other deep context does */
-  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !(c->mhc && c->deep_in8)))
+  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !((c->mhc || c->colour) && c->deep_in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

@@ -11,6 +11,28 @@
 
 #include "../../include/mibayer.h"
 
+/* The ranges mibayer_set_colour accepts (include/mibayer.h), shared by the context layer and the pool: the pool
+ * checks a stage when it is set and hands it to a shard only later, with the frames it belongs to. */
+static inline int mibayer_colour_in_range (const mibayer_colour *col)
+{
+  int k;
+  if (!col || col->struct_size != sizeof (mibayer_colour))
+    return 0;
+  for (k = 0; k < 3; k++)
+    if (col->black[k] < 0 || col->black[k] > 65535)
+      return 0;
+  for (k = 0; k < 9; k++)
+    if (col->matrix[k] < -65535 || col->matrix[k] > 65535)
+      return 0;
+  if (col->has_tone != 0 && col->has_tone != 1)
+    return 0;
+  if (col->has_tone)
+    for (k = 0; k < 257; k++)
+      if (col->tone[k] > 65536u)
+        return 0;
+  return 1;
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif

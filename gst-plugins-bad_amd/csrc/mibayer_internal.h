@@ -277,6 +277,29 @@ constexpr int kMhcRows = 16;
 hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1);
 
+/* Fused colour stage (MIBAYER_FLAG_COLOUR, bayer2rgb_colour_kernel): black level, Q12 matrix, tone curve on the
+ * demosaiced native-depth values, before the output conversion.  The matrix entry m is split as m = hi * 4096 + lo
+ * (hi = m >> 12 in [-16, 15], lo = m & 4095): sum (m v) = 4096 * sum (hi v) + sum (lo v) with v <= 65535, so both sums
+ * fit 32 bits (< 2^22 and < 2^30) and (acc + 2048) >> 12 = sum (hi v) + ((sum (lo v) + 2048) >> 12) exactly. */
+struct ColourStage {
+  int has_tone;
+  int black[3];                 /* R, G, B */
+  int m_hi[9], m_lo[9];         /* row-major, output channel x input channel */
+  uint32_t tone[257];
+};
+/* the kernel's argument: the deep kernel's (first, so that its list tables keep their offsets) + the stage; the tone
+ * table travels with every launch, so a launch keeps the table it was enqueued with */
+struct ColourParams {
+  DeepParams d;
+  int mhc;                      /* demosaic by the MHC filters (else the deep path's bilinear closed form) */
+  int in8, out16;
+  ColourStage s;
+};
+/* one kernel for both demosaic methods and all four input / output combinations (uniform run-time branches); chunks of
+ * kMhcRows rows, otherwise as launch_mhc */
+hipError_t launch_colour (const DeepParams &p, const ColourStage &s, bool mhc, bool in8, bool out16, int nframes,
+    hipStream_t stream, long long chunk0 = 0, long long nchunks = -1);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

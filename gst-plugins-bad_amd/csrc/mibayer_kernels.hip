@@ -1995,6 +1995,272 @@ hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, h
 }
 
 /* ------------------------------------------------------------------------- */
+/* fused colour stage (MIBAYER_FLAG_COLOUR)                                    */
+/* ------------------------------------------------------------------------- */
+/* Black level, Q12 colour matrix and tone curve (include/mibayer.h) on the demosaiced values while they are still
+ * integers in registers: no second pass over a 4- or 8-byte-per-pixel frame.  The rows go through the MHC kernel's
+ * unpacked window (mhc_row); R, G, B come from the MHC filters or from the deep path's bilinear closed form, which
+ * on that window is, with a = avg of the row's +-1 neighbours and u / d the rows up (j) / dn (j):
+ *   non-green site: C = S, G = avg (avg (S_u, S_d), a), D = avg (a_u, a_d);  green site: G = S, C = a, D = avg (S_u, S_d)
+ * (C the row's own colour, D the other one, as in the MHC kernel).  Reflect-101 columns give the reference's edge
+ * columns O[0] = S[1] and E[W-1] = S[W-2]; O[W-2] = S[W-3] is patched into the row (colour_row), and row H stands for
+ * dn (H-1) = dn_last instead of the reflected H-2.
+ *
+ * One kernel, no template fan-out: method, sample width, output width and tone curve are uniform run-time branches,
+ * and the row loop is rolled -- the window rotates through registers and the loads run kColourAhead rows ahead of it --
+ * which keeps the code a fraction of the four unrolled MHC kernels' (the library has a size cap; DESIGN.md 3b has what
+ * the rolled loop costs).  The tone table (257 dwords) is copied from the kernel
+ * arguments to LDS by the whole workgroup BEFORE the waves beyond the launch leave: no wave skips the barrier. */
+
+constexpr int kColourAhead = 4;
+
+/* row r of the frame, mapped into it: reflect-101 for the MHC filters, the reference's up () / dn () for bilinear */
+__device__ __forceinline__ DeepRaw colour_load (const ColourParams &cp, const uint8_t *src, int r, int g, int lane)
+{
+  const DeepParams &p = cp.d;
+  r = r < 0 ? -r : r;
+  if (cp.mhc)
+    r = r > p.height + 1 ? p.height - 1 : r >= p.height ? 2 * p.height - 2 - r : r;
+  else
+    r = r == p.height ? p.dn_last : r > p.height ? p.height - 1 : r;
+  if (cp.in8)
+    return deep_load<true> (p, src, r, g, lane);
+  return deep_load<false> (p, src, r, g, lane);
+}
+
+__device__ __forceinline__ MhcRow colour_row (const ColourParams &cp, const DeepRaw &raw, int lane, bool first,
+    int lastmode)
+{
+  MhcRow r;
+  if (cp.in8)
+    r = mhc_row<true> (cp.d, raw, lane, first, lastmode);
+  else
+    r = mhc_row<false> (cp.d, raw, lane, first, lastmode);
+  if (!cp.mhc) {
+    /* O[W-2] = S[W-3] (gstbayer2rgb.c:354-381): h2 of pixel W-1 is S[W-3] + S(W+1) = 2 S[W-3] by the reflection */
+    if (lastmode == 1)
+      r.h1[2] = r.h2[3];
+    if (lastmode == 2)
+      r.h1[0] = r.h2[1];
+  }
+  return r;
+}
+
+__device__ __forceinline__ int avg_i (int a, int b)
+{
+  return (a + b + 1) >> 1;
+}
+
+/* the deep path's bilinear values of pixel k of row z between rows u = up (j) and d = dn (j) */
+template <bool GREEN>
+__device__ __forceinline__ void bilinear_pixel (const MhcRow &u, const MhcRow &z, const MhcRow &d, int k, int &C, int &G,
+    int &D)
+{
+  const int a = (z.h1[k] + 1) >> 1;
+  const int vc = avg_i (u.c[k], d.c[k]);
+  if constexpr (GREEN) {
+    G = z.c[k];
+    C = a;
+    D = vc;
+  } else {
+    C = z.c[k];
+    G = avg_i (vc, a);
+    D = avg_i ((u.h1[k] + 1) >> 1, (d.h1[k] + 1) >> 1);
+  }
+}
+
+__global__ void __launch_bounds__ (256)
+bayer2rgb_colour_kernel (ColourParams cp)
+{
+  __shared__ uint32_t tone[257];
+  const DeepParams &p = cp.d;
+  if (cp.s.has_tone) {
+    /* kernarg_table_entry at a per-lane index: not the scalar load its other users get, a vector load from the
+     * constant address space -- 257 dwords once per workgroup */
+    constexpr size_t kToneOffset = offsetof (ColourParams, s) + offsetof (ColourStage, tone);
+    tone[threadIdx.x] = kernarg_table_entry<uint32_t> (kToneOffset, threadIdx.x);
+    if (threadIdx.x == 0)
+      tone[256] = kernarg_table_entry<uint32_t> (kToneOffset, 256);
+    __syncthreads ();
+  }
+  const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (wave >= p.nwaves)
+    return;
+  const int lane = (int) (threadIdx.x & 63u);
+  const uint32_t crow = fastdiv (wave, p.div_tiles_x);
+  const uint32_t tx = wave - crow * p.div_tiles_x.d;
+  const uint32_t chunk = p.chunk0 + crow;
+  const uint32_t frame = fastdiv (chunk, p.div_chunks);
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kMhcRows;
+  const int y1 = y0 + kMhcRows < p.height ? y0 + kMhcRows : p.height;
+  const uint8_t *src = p.nlist
+      ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
+  uint8_t *dst = p.nlist
+      ? kernarg_table_entry<uint8_t *> (offsetof (DeepParams, dst_list), frame) : p.dst + frame * p.dst_frame_bytes;
+  const int g = (int) tx * 64 + lane;
+  const bool first = g == 0;
+  const int lastmode = g == p.groups - 1 ? ((p.width & 3) ? 2 : 1) : 0;
+  const bool store = g < p.groups;
+  const bool full = 4 * g + 4 <= p.width;
+  const int s = p.out_shift;
+  const int tshift = cp.out16 ? s : 8 - s;              /* 16 - depth */
+
+  /* rows y0-2 .. y0+1 fill the window, rows y0+2 .. run kColourAhead loads ahead of it */
+  MhcRow w0, w1, w2, w3;
+  DeepRaw ring[kColourAhead];
+  {
+    DeepRaw head[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      head[i] = colour_load (cp, src, y0 - 2 + i, g, lane);
+#pragma unroll
+    for (int i = 0; i < kColourAhead; i++)
+      ring[i] = colour_load (cp, src, y0 + 2 + i, g, lane);
+    w0 = colour_row (cp, head[0], lane, first, lastmode);
+    w1 = colour_row (cp, head[1], lane, first, lastmode);
+    w2 = colour_row (cp, head[2], lane, first, lastmode);
+    w3 = colour_row (cp, head[3], lane, first, lastmode);
+  }
+#pragma unroll 1
+  for (int j = y0; j < y1; j++) {
+    const MhcRow w4 = colour_row (cp, ring[0], lane, first, lastmode);
+#pragma unroll
+    for (int i = 0; i + 1 < kColourAhead; i++)
+      ring[i] = ring[i + 1];
+    if (j + 2 + kColourAhead <= y1 + 1)                 /* the last output row, y1 - 1, needs row y1 + 1 */
+      ring[kColourAhead - 1] = colour_load (cp, src, j + 2 + kColourAhead, g, lane);
+    int C[4], G[4], D[4];
+    const bool green_even = ((j & 1) ^ p.mhc_green_odd) == 0;
+    if (cp.mhc) {
+      if (green_even) {
+        mhc_pixel<true> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
+        mhc_pixel<false> (p, w0, w1, w2, w3, w4, 1, C[1], G[1], D[1]);
+        mhc_pixel<true> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
+        mhc_pixel<false> (p, w0, w1, w2, w3, w4, 3, C[3], G[3], D[3]);
+      } else {
+        mhc_pixel<false> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
+        mhc_pixel<true> (p, w0, w1, w2, w3, w4, 1, C[1], G[1], D[1]);
+        mhc_pixel<false> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
+        mhc_pixel<true> (p, w0, w1, w2, w3, w4, 3, C[3], G[3], D[3]);
+      }
+    } else if (green_even) {
+      bilinear_pixel<true> (w1, w2, w3, 0, C[0], G[0], D[0]);
+      bilinear_pixel<false> (w1, w2, w3, 1, C[1], G[1], D[1]);
+      bilinear_pixel<true> (w1, w2, w3, 2, C[2], G[2], D[2]);
+      bilinear_pixel<false> (w1, w2, w3, 3, C[3], G[3], D[3]);
+    } else {
+      bilinear_pixel<false> (w1, w2, w3, 0, C[0], G[0], D[0]);
+      bilinear_pixel<true> (w1, w2, w3, 1, C[1], G[1], D[1]);
+      bilinear_pixel<false> (w1, w2, w3, 2, C[2], G[2], D[2]);
+      bilinear_pixel<true> (w1, w2, w3, 3, C[3], G[3], D[3]);
+    }
+    /* the colour stage: (R, G, B) -> black level -> matrix -> clamp, 24-bit multiplies on the split entries */
+    const bool c_is_red = ((j & 1) ^ p.mhc_red_odd) == 0;
+    int v[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = max ((c_is_red ? C[i] : D[i]) - cp.s.black[0], 0);
+      const int gr = max (G[i] - cp.s.black[1], 0);
+      const int b = max ((c_is_red ? D[i] : C[i]) - cp.s.black[2], 0);
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        const int hi = __mul24 (cp.s.m_hi[3 * ch], r) + __mul24 (cp.s.m_hi[3 * ch + 1], gr)
+            + __mul24 (cp.s.m_hi[3 * ch + 2], b);
+        const uint32_t lo = __umul24 ((uint32_t) cp.s.m_lo[3 * ch], (uint32_t) r)
+            + __umul24 ((uint32_t) cp.s.m_lo[3 * ch + 1], (uint32_t) gr)
+            + __umul24 ((uint32_t) cp.s.m_lo[3 * ch + 2], (uint32_t) b);
+        v[i][ch] = min (max (hi + (int) ((lo + 2048u) >> 12), 0), p.mhc_max);
+      }
+    }
+    uint32_t o[4][3];
+    if (cp.s.has_tone) {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+          const uint32_t t = (uint32_t) v[i][ch] << tshift;
+          const uint32_t ti = t >> 8, tf = t & 255u;
+          const uint32_t q = min ((__umul24 (tone[ti], 256u - tf) + __umul24 (tone[ti + 1], tf) + 128u) >> 8, 65535u);
+          o[i][ch] = cp.out16 ? q : q >> 8;
+        }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++)
+          o[i][ch] = cp.out16 ? (uint32_t) v[i][ch] << s : (uint32_t) v[i][ch] >> s;
+    }
+    /* the MHC kernel's packing and stores with C = R, D = B: x = [R, G], y = [B, 0] */
+    uint32_t x[4], y[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      x[i] = o[i][0] | (o[i][1] << 16);
+      y[i] = o[i][2];
+    }
+    uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
+    const uint32_t s0 = p.mhc_sel[0][0], s1 = p.mhc_sel[0][1];
+    if (cp.out16) {
+      u32x4 v0, v1;
+      v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+      v0.y = __builtin_amdgcn_perm (x[0], y[0], s1);
+      v0.z = __builtin_amdgcn_perm (x[1], y[1], s0);
+      v0.w = __builtin_amdgcn_perm (x[1], y[1], s1);
+      v1.x = __builtin_amdgcn_perm (x[2], y[2], s0);
+      v1.y = __builtin_amdgcn_perm (x[2], y[2], s1);
+      v1.z = __builtin_amdgcn_perm (x[3], y[3], s0);
+      v1.w = __builtin_amdgcn_perm (x[3], y[3], s1);
+      const int kq = lane & 3;
+      u32x4 s0v, s1v;
+      deep_quad_pieces (v0, v1, kq, s0v, s1v);
+      const int qg = g - kq;
+      const int ga = qg + (kq >> 1), gb = qg + 2 + (kq >> 1);
+      if (ga < p.groups && ((kq & 1) == 0 || 4 * ga + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * kq) = s0v;
+      if (gb < p.groups && ((kq & 1) == 0 || 4 * gb + 4 <= p.width))
+        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * kq) = s1v;
+    } else {
+      u32x4 vv;
+      vv.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+      vv.y = __builtin_amdgcn_perm (x[1], y[1], s0);
+      vv.z = __builtin_amdgcn_perm (x[2], y[2], s0);
+      vv.w = __builtin_amdgcn_perm (x[3], y[3], s0);
+      if (store) {
+        uint8_t *q = out + 16 * (size_t) g;
+        if (full) {
+          __builtin_nontemporal_store (vv, (u32x4_a4 *) q);
+        } else {
+          const u32x2_a4 two = { vv.x, vv.y };
+          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+        }
+      }
+    }
+    w0 = w1;
+    w1 = w2;
+    w2 = w3;
+    w3 = w4;
+  }
+}
+
+hipError_t launch_colour (const DeepParams &p, const ColourStage &s, bool mhc, bool in8, bool out16, int nframes,
+    hipStream_t stream, long long chunk0, long long nchunks)
+{
+  if (p.width < 4 || p.height < 3 || (p.width & 1))
+    return hipErrorInvalidValue;
+  ColourParams q;
+  q.d = p;
+  unsigned grid = 0;
+  const hipError_t e = deep_grid (q.d, kMhcRows, nframes, chunk0, nchunks, &grid);
+  if (e != hipSuccess || grid == 0)
+    return e;
+  q.mhc = mhc;
+  q.in8 = in8;
+  q.out16 = out16;
+  q.s = s;
+  hipLaunchKernelGGL (bayer2rgb_colour_kernel, dim3 (grid), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

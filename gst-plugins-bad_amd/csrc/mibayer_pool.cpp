@@ -52,11 +52,17 @@
  */
 #include "mibayer_hooks.h"
 
+/* the context layer's colour entry points are bound weakly: the pool logic also links against test doubles of that
+ * layer that do not have them (tests/check), where a colour request is refused */
+#pragma weak mibayer_set_colour
+#pragma weak mibayer_get_colour
+
 #include <sched.h>
 
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdio.h>
@@ -89,6 +95,9 @@ struct Frame {
   int state;    /* FrameState; helper-thread frames: under Shard::mu */
   int rc;
   bool submitted;       /* handed to the context of `shard` (its ring may hold it) */
+  /* MIBAYER_FLAG_COLOUR pools: the stage the pool held when mibayer_pool_submit accepted the frame; whoever hands the
+   * frame to a context -- the caller's thread, a helper thread later, a redo on another shard -- applies it first */
+  std::shared_ptr<const mibayer_colour> colour;
 };
 
 struct Shard {
@@ -100,6 +109,8 @@ struct Shard {
   long long assigned = 0;       /* frames routed here so far (balance of the NUMA-local routing) */
   long long stall_after = -1;   /* MIBAYER_INJECT_STALL: stall the compute queue once this many frames were routed here */
   int stall_ms = 0;
+  std::shared_ptr<const mibayer_colour> applied;        /* the stage its context holds (touched by whichever ONE
+                                                           thread hands frames to the context) */
   std::atomic<long long> completions { 0 };
   std::atomic<long long> fail_after { -1 };     /* fault injection; -1 = never */
   /* helper thread */
@@ -126,6 +137,16 @@ struct Shard {
     return at >= 0 && n > at;
   }
 };
+
+/* the context of `sh` gets the frame's colour stage unless it holds it already: call right before the frame is handed
+ * to the context, on the thread that hands it over */
+void apply_colour (Shard *sh, const Frame *f)
+{
+  if (!f->colour || f->colour == sh->applied || !mibayer_set_colour)
+    return;
+  if (mibayer_set_colour (sh->ctx, f->colour.get ()) == MIBAYER_OK)
+    sh->applied = f->colour;
+}
 
 bool device_failure (int rc)
 {
@@ -227,6 +248,7 @@ void helper_main (Shard *sh)
       f->submitted = true;      /* from here on the context may hold it */
       sh->ring.push_back (f);
       lk.unlock ();
+      apply_colour (sh, f);
       const int rc = mibayer_submit (sh->ctx, f->src, f->dst, f);
       lk.lock ();
       if (rc != MIBAYER_OK) {
@@ -288,6 +310,9 @@ struct mibayer_pool {
   /* frames lost on a device that ran into the wait deadline: their buffers are the device's until it settles */
   struct Lost { void *tag; int shard; };
   std::vector<Lost> lost;
+  /* MIBAYER_FLAG_COLOUR: the stage of the frames submitted from now on (NULL: not a colour pool); only the
+   * caller's thread touches it, the frames carry their own reference */
+  std::shared_ptr<const mibayer_colour> colour;
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -469,6 +494,16 @@ extern "C" int mibayer_pool_create (const mibayer_pool_cfg *cfg,
   if (const char *e = getenv ("MIBAYER_POOL_HELPERS"))
     pool->use_helpers = atoi (e) != 0;
   pool->inverse = (cfg->stream.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
+  if ((cfg->stream.flags & MIBAYER_FLAG_COLOUR) && mibayer_get_colour) {
+    /* what the new contexts hold (the identity): frames submitted before any mibayer_pool_set_colour carry it, so a
+     * redo on a shard that has moved on since still converts them as they were submitted */
+    mibayer_colour first;
+    if (mibayer_get_colour (pool->shards[0]->ctx, &first) == MIBAYER_OK) {
+      pool->colour = std::make_shared<const mibayer_colour> (first);
+      for (Shard *sh : pool->shards)
+        sh->applied = pool->colour;
+    }
+  }
   {
     int first = -2;
     for (Shard *sh : pool->shards) {
@@ -602,6 +637,19 @@ extern "C" int mibayer_pool_set_wait_timeout (mibayer_pool *pool, int ms)
   return MIBAYER_OK;
 }
 
+/* The colour stage of the frames submitted from now on.  Nothing is handed to a context here: the pool keeps the
+ * stage, every frame takes a reference when mibayer_pool_submit accepts it, and the thread that later gives the frame
+ * to a shard's context -- the caller's, the shard's helper thread, a redo on a surviving shard after a failover -- sets
+ * the context's stage first (apply_colour).  So a frame that waits in a helper's queue, or is converted again on
+ * another device, keeps the parameters it was submitted with, and no frame sees two. */
+extern "C" int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour *colour)
+{
+  if (!pool || !pool->colour || !mibayer_set_colour || !mibayer_colour_in_range (colour))
+    return MIBAYER_ERR_ARG;     /* not a colour pool (or no colour stage in this library), or values out of range */
+  pool->colour = std::make_shared<const mibayer_colour> (*colour);
+  return MIBAYER_OK;
+}
+
 extern "C" int mibayer_pool_inject_stall (mibayer_pool *pool, int shard, int ms)
 {
   if (!pool || shard < 0 || shard >= (int) pool->shards.size ())
@@ -689,7 +737,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       sh->stall_ms = 0;
       (void) mibayer_internal_stall (sh->ctx, ms);
     }
-    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false };
+    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour };
     if (pool->use_helpers && (mibayer_internal_is_pageable (src) || mibayer_internal_is_pageable (dst))
         && !sh->pageable_seen) {
       sh->pageable_seen = true;
@@ -699,6 +747,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       pool->fifo.push_back (f);
       queue_to_helper (sh, &pool->fifo.back ());
     } else {
+      apply_colour (sh, &f);
       const int rc = mibayer_submit (sh->ctx, src, dst, tag);
       if (device_failure (rc)) {
         kill_shard (pool, (int) idx, rc, mibayer_last_hip_error ());
@@ -804,6 +853,7 @@ extern "C" int mibayer_pool_wait (mibayer_pool *pool, void **tag)
     }
     f.submitted = true;         /* while the spare slot of `to` works on it */
     f.state = F_REDO;
+    apply_colour (to, &f);
     int rc = mibayer_internal_run_spare (to->ctx, f.src, f.dst);
     if (rc == MIBAYER_OK && to->fault_due ())
       rc = MIBAYER_ERR_HIP;

@@ -49,6 +49,9 @@
 #include "gstmibayerelement.h"
 #include "gstmihostpool.h"
 
+#define GST_MI_COLOUR_TONE_TYPE_NAME MIBAYER_TYPE_NAME ("Bayer2RGBToneCurve")
+#include "gstmicolour.h"
+
 #define MI_BAYER_METHOD_TYPE_NAME MIBAYER_TYPE_NAME ("Bayer2RGBMethod")
 
 /* each element logs into its own category, named like the reference's
@@ -76,7 +79,9 @@ enum
   PROP_HIPGRAPH,
   PROP_PINNED_POOL,
   PROP_TIMEOUT_MS,
-  PROP_METHOD
+  PROP_METHOD,
+  PROP_COLOUR_FIRST,            /* GST_MI_COLOUR_N_PROPS ids (gstmicolour.h) */
+  PROP_COLOUR_LAST = PROP_COLOUR_FIRST + GST_MI_COLOUR_N_PROPS - 1
 };
 
 #define DEFAULT_DEVICE_ID 0
@@ -422,6 +427,8 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
 {
   const gboolean inverse = IS_INVERSE (self);
   mibayer_pool_cfg pc;
+  mibayer_colour colour;
+  gboolean want_colour;
   int rc;
 
   if (self->pool && self->pool_stride == video_stride)
@@ -454,6 +461,18 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
   self->pool_stride = 0;
   self->capacity = 0;
 
+  /* the colour stage: only when a colour property is off its default (the default output is the reference's bytes) */
+  want_colour = !inverse && !gst_mi_colour_props_are_default (self->act.colour);
+  if (want_colour) {
+    gchar *why = NULL;
+    if (!gst_mi_colour_props_build (self->act.colour, &colour, &why) || !mibayer_pool_set_colour) {
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up the colour stage", LABEL (self)),
+          why ? why : g_strdup ("this libmibayer has no colour stage"));
+      return FALSE;
+    }
+  }
+
   memset (&pc, 0, sizeof pc);
   pc.struct_size = sizeof pc;
   pc.stream.struct_size = sizeof pc.stream;
@@ -476,7 +495,8 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       | MIBAYER_FLAG_SRC_BITS (self->src_bits)
       | (self->src_big_endian ? MIBAYER_FLAG_SRC_BIG_ENDIAN : 0)
       | (self->out16 ? MIBAYER_FLAG_DST_16BIT : 0)
-      | (!inverse && self->act.method == GST_MI_BAYER_METHOD_MHC ? MIBAYER_FLAG_MHC : 0);
+      | (!inverse && self->act.method == GST_MI_BAYER_METHOD_MHC ? MIBAYER_FLAG_MHC : 0)
+      | (want_colour ? MIBAYER_FLAG_COLOUR : 0);
   if (!element_parse_devices (self, &pc)) {
     element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
         g_strdup_printf ("%s: cannot parse devices=\"%s\"", LABEL (self),
@@ -505,6 +525,14 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
           g_strdup_printf ("%s %s", mibayer_strerror (rc),
               mibayer_last_hip_error ()));
     }
+    return FALSE;
+  }
+  if (want_colour && (rc = mibayer_pool_set_colour (self->pool, &colour)) != MIBAYER_OK) {
+    mibayer_pool_destroy (self->pool);
+    self->pool = NULL;
+    element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+        g_strdup_printf ("%s: cannot set up the colour stage", LABEL (self)),
+        g_strdup_printf ("mibayer_pool_set_colour: %s", mibayer_strerror (rc)));
     return FALSE;
   }
   /* a GPU that stops answering is dropped like one that reports an error, after this long */
@@ -558,6 +586,8 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
       self->method = g_value_get_enum (value);
       break;
     default:
+      if (gst_mi_colour_set_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
+        break;
       G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
       break;
   }
@@ -594,6 +624,8 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
       g_value_set_enum (value, self->method);
       break;
     default:
+      if (gst_mi_colour_get_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
+        break;
       G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
       break;
   }
@@ -612,6 +644,13 @@ element_finalize (GObject * object)
   self->act.devices = NULL;
   g_free (self->failure_note);
   self->failure_note = NULL;
+  if (self->colour) {
+    gst_mi_colour_props_clear (self->colour);
+    gst_mi_colour_props_clear (self->act.colour);
+    g_free (self->colour);
+    g_free (self->act.colour);
+    self->colour = self->act.colour = NULL;
+  }
   g_free (self->error_text);
   g_free (self->error_debug);
   self->error_text = self->error_debug = NULL;
@@ -1162,6 +1201,7 @@ element_start (GstBaseTransform * base)
   self->act.pinned_pool = self->pinned_pool;
   self->act.timeout_ms = self->timeout_ms;
   self->act.method = self->method;
+  gst_mi_colour_props_copy (self->act.colour, self->colour);
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
   self->prerolled = FALSE;
@@ -1244,6 +1284,8 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             "stock element)", gst_mi_bayer_method_get_type (), DEFAULT_METHOD,
             G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
             G_PARAM_STATIC_STRINGS));
+  if (!inverse)
+    gst_mi_colour_install_properties (object_class, PROP_COLOUR_FIRST);
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
   transform_class->get_unit_size = GST_DEBUG_FUNCPTR (element_get_unit_size);
@@ -1274,6 +1316,10 @@ gst_mi_bayer_element_instance_setup (GstMiBayerElement * self)
   self->act.timeout_ms = DEFAULT_TIMEOUT_MS;
   self->method = DEFAULT_METHOD;
   self->act.method = DEFAULT_METHOD;
+  self->colour = g_new0 (GstMiColourProps, 1);
+  self->act.colour = g_new0 (GstMiColourProps, 1);
+  gst_mi_colour_props_init (self->colour);
+  gst_mi_colour_props_init (self->act.colour);
   self->error_text = self->error_debug = NULL;
   self->act.device_id = DEFAULT_DEVICE_ID;
   self->act.devices = NULL;

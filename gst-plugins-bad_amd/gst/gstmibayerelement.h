@@ -60,6 +60,7 @@ struct _GstMiBayerElement
   gboolean pinned_pool;
   gint timeout_ms;              /* deadline of every wait for a GPU; 0 = none */
   gint method;                  /* GstMiBayerMethod (bayer2rgb only) */
+  gpointer colour;              /* GstMiColourProps* (gstmicolour.h; bayer2rgb only): the colour-stage properties */
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -72,6 +73,7 @@ struct _GstMiBayerElement
     gboolean pinned_pool;
     gint timeout_ms;
     gint method;
+    gpointer colour;            /* GstMiColourProps* */
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;

@@ -1,0 +1,241 @@
+/*
+ * gstmicolour.h -- the colour-stage properties of bayer2rgb and hipbayer2rgb (MIBAYER_FLAG_COLOUR, include/mibayer.h):
+ * black-level, red-/green-/blue-gain, ccm, tone-curve, gamma.  One definition for both plugins; each includes this
+ * header once, after defining GST_MI_COLOUR_TONE_TYPE_NAME (the two plugins may be loaded into one process, so the
+ * enum type needs a name per plugin).
+ *
+ * With every property at its default an element does not set the flag: its output stays the reference's bytes.
+ *
+ * The colour entry points of libmibayer are bound WEAKLY: the plugins also load against builds of the library
+ * interface that do not have them (the test doubles of tests/check), where a non-default colour request ends in an
+ * element error and the defaults call none of them.
+ */
+#ifndef GST_MI_COLOUR_H
+#define GST_MI_COLOUR_H
+
+#include <gst/gst.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "mibayer.h"
+
+#pragma weak mibayer_colour_init
+#pragma weak mibayer_colour_matrix
+#pragma weak mibayer_colour_tone
+#pragma weak mibayer_set_colour
+#pragma weak mibayer_pool_set_colour
+
+typedef struct
+{
+  guint black_level;
+  gdouble gain[3];              /* red, green, blue */
+  gchar *ccm;                   /* nine comma-separated numbers, row-major; NULL / "" = identity */
+  gint tone_curve;              /* MIBAYER_TONE_* */
+  gdouble gamma;
+} GstMiColourProps;
+
+/* the ids an element's property enum reserves, in this order, from its `first` id on */
+enum
+{
+  GST_MI_COLOUR_PROP_BLACK_LEVEL = 0,
+  GST_MI_COLOUR_PROP_RED_GAIN,
+  GST_MI_COLOUR_PROP_GREEN_GAIN,
+  GST_MI_COLOUR_PROP_BLUE_GAIN,
+  GST_MI_COLOUR_PROP_CCM,
+  GST_MI_COLOUR_PROP_TONE_CURVE,
+  GST_MI_COLOUR_PROP_GAMMA,
+  GST_MI_COLOUR_N_PROPS
+};
+
+#define GST_MI_COLOUR_DEFAULT_GAMMA 2.2
+
+static GType
+gst_mi_colour_tone_get_type (void)
+{
+  static gsize type = 0;
+  static const GEnumValue values[] = {
+    {MIBAYER_TONE_LINEAR, "Linear: no tone curve", "linear"},
+    {MIBAYER_TONE_SRGB, "The sRGB transfer function", "srgb"},
+    {MIBAYER_TONE_GAMMA, "Power law x^(1/gamma), see the gamma property", "gamma"},
+    {0, NULL, NULL}
+  };
+  if (g_once_init_enter (&type)) {
+    GType t = g_enum_register_static (GST_MI_COLOUR_TONE_TYPE_NAME, values);
+    g_once_init_leave (&type, t);
+  }
+  return (GType) type;
+}
+
+static void
+gst_mi_colour_props_init (GstMiColourProps * p)
+{
+  p->black_level = 0;
+  p->gain[0] = p->gain[1] = p->gain[2] = 1.0;
+  p->ccm = NULL;
+  p->tone_curve = MIBAYER_TONE_LINEAR;
+  p->gamma = GST_MI_COLOUR_DEFAULT_GAMMA;
+}
+
+static void
+gst_mi_colour_props_clear (GstMiColourProps * p)
+{
+  g_free (p->ccm);
+  p->ccm = NULL;
+}
+
+/* dst = src (dst holds a valid or NULL ccm) */
+static G_GNUC_UNUSED void
+gst_mi_colour_props_copy (GstMiColourProps * dst, const GstMiColourProps * src)
+{
+  gchar *ccm = g_strdup (src->ccm);
+  g_free (dst->ccm);
+  *dst = *src;
+  dst->ccm = ccm;
+}
+
+/* gamma alone changes nothing: it is read by tone-curve=gamma only */
+static gboolean
+gst_mi_colour_props_are_default (const GstMiColourProps * p)
+{
+  return p->black_level == 0 && p->gain[0] == 1.0 && p->gain[1] == 1.0 && p->gain[2] == 1.0
+      && (p->ccm == NULL || p->ccm[0] == '\0') && p->tone_curve == MIBAYER_TONE_LINEAR;
+}
+
+/* The mibayer_colour of the properties, built with the library's helpers so that everybody rounds alike.  FALSE with a
+ * message (g_free) when the ccm string does not parse, a value is out of range or the library has no colour stage. */
+static gboolean
+gst_mi_colour_props_build (const GstMiColourProps * p, mibayer_colour * out, gchar ** message)
+{
+  double ccm[9];
+  gboolean have_ccm = p->ccm != NULL && p->ccm[0] != '\0';
+
+  *message = NULL;
+  if (!mibayer_colour_init || !mibayer_colour_matrix || !mibayer_colour_tone) {
+    *message = g_strdup ("this libmibayer has no colour stage (mibayer_colour_* are missing)");
+    return FALSE;
+  }
+  if (have_ccm) {
+    const gchar *s = p->ccm;
+    gint k;
+    for (k = 0; k < 9; k++) {
+      gchar *end = NULL;
+      ccm[k] = g_ascii_strtod (s, &end);
+      if (end == s)
+        break;
+      s = end;
+      while (*s == ' ')
+        s++;
+      if (k < 8) {
+        if (*s != ',')
+          break;
+        s++;
+      }
+    }
+    if (k < 9 || *s != '\0') {
+      *message = g_strdup_printf ("ccm=\"%s\" is not nine comma-separated numbers", p->ccm);
+      return FALSE;
+    }
+  }
+  mibayer_colour_init (out);
+  out->black[0] = out->black[1] = out->black[2] = (int32_t) p->black_level;
+  if (mibayer_colour_matrix (p->gain, have_ccm ? ccm : NULL, out->matrix) != MIBAYER_OK) {
+    *message = g_strdup ("gains x ccm leave the matrix range (-15.99 .. 15.99 per entry)");
+    return FALSE;
+  }
+  if (p->tone_curve != MIBAYER_TONE_LINEAR) {
+    if (mibayer_colour_tone (p->tone_curve, p->gamma, out->tone) != MIBAYER_OK) {
+      *message = g_strdup_printf ("tone-curve %d with gamma=%g is not valid", p->tone_curve, p->gamma);
+      return FALSE;
+    }
+    out->has_tone = 1;
+  }
+  return TRUE;
+}
+
+static void
+gst_mi_colour_install_properties (GObjectClass * object_class, guint first)
+{
+  const GParamFlags flags = G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY | G_PARAM_STATIC_STRINGS;
+  static const gchar *const gain_name[3] = { "red-gain", "green-gain", "blue-gain" };
+  static const gchar *const gain_nick[3] = { "Red gain", "Green gain", "Blue gain" };
+  gint k;
+
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_BLACK_LEVEL,
+      g_param_spec_uint ("black-level", "Black level",
+          "Subtracted from every demosaiced channel, at the sensor's native depth "
+          "(colour stage fused into the demosaic kernel; any non-default colour "
+          "property turns it on, and the output is then no longer the stock element's)",
+          0, 65535, 0, flags));
+  for (k = 0; k < 3; k++)
+    g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_RED_GAIN + k,
+        g_param_spec_double (gain_name[k], gain_nick[k],
+            "White-balance gain of the channel, applied before ccm", 0.0, 15.99, 1.0, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_CCM,
+      g_param_spec_string ("ccm", "Colour correction matrix",
+          "Nine comma-separated numbers, row-major (output R, G, B from input R, G, B); "
+          "empty = identity.  gains x ccm entries must stay within +-15.99", "", flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_TONE_CURVE,
+      g_param_spec_enum ("tone-curve", "Tone curve",
+          "Transfer curve applied after the matrix", gst_mi_colour_tone_get_type (),
+          MIBAYER_TONE_LINEAR, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_GAMMA,
+      g_param_spec_double ("gamma", "Gamma",
+          "Exponent of tone-curve=gamma: out = in^(1/gamma)", 0.01, 100.0,
+          GST_MI_COLOUR_DEFAULT_GAMMA, flags));
+}
+
+/* TRUE when `id` (relative to the element's first colour id) is a colour property; the caller holds its lock */
+static gboolean
+gst_mi_colour_set_property (GstMiColourProps * p, gint id, const GValue * value)
+{
+  switch (id) {
+    case GST_MI_COLOUR_PROP_BLACK_LEVEL:
+      p->black_level = g_value_get_uint (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_RED_GAIN:
+    case GST_MI_COLOUR_PROP_GREEN_GAIN:
+    case GST_MI_COLOUR_PROP_BLUE_GAIN:
+      p->gain[id - GST_MI_COLOUR_PROP_RED_GAIN] = g_value_get_double (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_CCM:
+      g_free (p->ccm);
+      p->ccm = g_value_dup_string (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_TONE_CURVE:
+      p->tone_curve = g_value_get_enum (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_GAMMA:
+      p->gamma = g_value_get_double (value);
+      return TRUE;
+    default:
+      return FALSE;
+  }
+}
+
+static gboolean
+gst_mi_colour_get_property (const GstMiColourProps * p, gint id, GValue * value)
+{
+  switch (id) {
+    case GST_MI_COLOUR_PROP_BLACK_LEVEL:
+      g_value_set_uint (value, p->black_level);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_RED_GAIN:
+    case GST_MI_COLOUR_PROP_GREEN_GAIN:
+    case GST_MI_COLOUR_PROP_BLUE_GAIN:
+      g_value_set_double (value, p->gain[id - GST_MI_COLOUR_PROP_RED_GAIN]);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_CCM:
+      g_value_set_string (value, p->ccm ? p->ccm : "");
+      return TRUE;
+    case GST_MI_COLOUR_PROP_TONE_CURVE:
+      g_value_set_enum (value, p->tone_curve);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_GAMMA:
+      g_value_set_double (value, p->gamma);
+      return TRUE;
+    default:
+      return FALSE;
+  }
+}
+
+#endif /* GST_MI_COLOUR_H */

@@ -31,6 +31,9 @@
 #include "gstmihostpool.h"
 #include "mibayer.h"
 
+#define GST_MI_COLOUR_TONE_TYPE_NAME "GstMiHipBayer2RGBToneCurve"
+#include "gstmicolour.h"
+
 GST_DEBUG_CATEGORY_STATIC (gst_mi_hip_debug);
 #define GST_CAT_DEFAULT gst_mi_hip_debug
 
@@ -45,7 +48,9 @@ enum
   PROP_AUTOTUNE,
   PROP_PLAN,
   PROP_OVERLAP,
-  PROP_METHOD
+  PROP_METHOD,
+  PROP_COLOUR_FIRST,            /* GST_MI_COLOUR_N_PROPS ids (gstmicolour.h) */
+  PROP_COLOUR_LAST = PROP_COLOUR_FIRST + GST_MI_COLOUR_N_PROPS - 1
 };
 
 /* hipbayer2rgb's `method` (values as bayer2rgb's): the reference's bilinear demosaic or Malvar-He-Cutler */
@@ -819,7 +824,8 @@ typedef struct
   guint busy_run;               /* consecutive frames that arrived while the previous conversion was still running */
   gchar plan[160];              /* property "plan" (read-only): the context's launch plan and where it came from */
   gint method;                  /* property "method" (HB2R_METHOD_*; g_atomic_int_*), read when a context is made */
-  gboolean ctx_mhc;             /* the context runs the MHC kernel: one kernel shape, no plan to measure */
+  gboolean ctx_single_shape;    /* the context runs the MHC or the colour kernel: one kernel shape, no plan to measure */
+  GstMiColourProps colour;      /* the colour-stage properties (object lock), read when a context is made */
   gboolean prerolled;           /* a frame has left since start / flush: batching may begin */
   GQueue waiting;               /* Hb2rPair* */
   GQueue ready;                 /* GstBuffer* */
@@ -924,7 +930,12 @@ hb2r_set_property (GObject * object, guint prop_id, const GValue * value,
   else if (prop_id == PROP_METHOD)
     g_atomic_int_set (&((GstMiHipBayer2RGB *) object)->method,
         g_value_get_enum (value));
-  else
+  else if (prop_id >= PROP_COLOUR_FIRST && prop_id <= PROP_COLOUR_LAST) {
+    GST_OBJECT_LOCK (object);
+    (void) gst_mi_colour_set_property (&((GstMiHipBayer2RGB *) object)->colour,
+        (gint) prop_id - PROP_COLOUR_FIRST, value);
+    GST_OBJECT_UNLOCK (object);
+  } else
     G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
 }
 
@@ -949,6 +960,11 @@ hb2r_get_property (GObject * object, guint prop_id, GValue * value,
   else if (prop_id == PROP_PLAN) {
     GST_OBJECT_LOCK (object);
     g_value_set_string (value, ((GstMiHipBayer2RGB *) object)->plan);
+    GST_OBJECT_UNLOCK (object);
+  } else if (prop_id >= PROP_COLOUR_FIRST && prop_id <= PROP_COLOUR_LAST) {
+    GST_OBJECT_LOCK (object);
+    (void) gst_mi_colour_get_property (&((GstMiHipBayer2RGB *) object)->colour,
+        (gint) prop_id - PROP_COLOUR_FIRST, value);
     GST_OBJECT_UNLOCK (object);
   } else
     G_OBJECT_WARN_INVALID_PROPERTY_ID (object, prop_id, pspec);
@@ -975,6 +991,7 @@ hb2r_finalize (GObject * object)
   hb2r_drop_queued ((GstMiHipBayer2RGB *) object);
   hb2r_drop_ctx ((GstMiHipBayer2RGB *) object);
   hb2r_drop_out_pool ((GstMiHipBayer2RGB *) object);
+  gst_mi_colour_props_clear (&((GstMiHipBayer2RGB *) object)->colour);
   G_OBJECT_CLASS (gst_mi_hip_bayer2rgb_parent_class)->finalize (object);
 }
 
@@ -1106,7 +1123,7 @@ hb2r_note_plan (GstMiHipBayer2RGB * self)
   int variant = 0, band = 0, align = 0, src = -1;
   const char *name;
 
-  if (self->ctx_mhc) {          /* one kernel shape, nothing to choose */
+  if (self->ctx_single_shape) {          /* one kernel shape, nothing to choose */
     GST_OBJECT_LOCK (self);
     g_snprintf (self->plan, sizeof self->plan, "%s source=default", mibayer_ctx_variant_name (self->ctx));
     GST_OBJECT_UNLOCK (self);
@@ -1128,11 +1145,30 @@ static gboolean
 hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
 {
   mibayer_cfg cfg;
+  mibayer_colour colour;
+  gboolean want_colour = FALSE;
   int rc;
 
   if (self->ctx != NULL && self->ctx_device == device)
     return TRUE;
   hb2r_drop_ctx (self);
+  /* the colour stage: only when a colour property is off its default (the default output is the reference's bytes) */
+  if (!HB2R_INVERSE (self)) {
+    gchar *why = NULL;
+    gboolean ok = TRUE;
+    GST_OBJECT_LOCK (self);
+    want_colour = !gst_mi_colour_props_are_default (&self->colour);
+    if (want_colour)
+      ok = gst_mi_colour_props_build (&self->colour, &colour, &why) && mibayer_set_colour != NULL;
+    GST_OBJECT_UNLOCK (self);
+    if (!ok) {
+      GST_ELEMENT_ERROR (self, LIBRARY, SETTINGS,
+          ("%s: cannot set up the colour stage", HB2R_LABEL (self)),
+          ("%s", why ? why : "this libmibayer has no colour stage"));
+      g_free (why);
+      return FALSE;
+    }
+  }
   memset (&cfg, 0, sizeof cfg);
   cfg.struct_size = sizeof cfg;
   cfg.width = self->width;
@@ -1143,10 +1179,20 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
   cfg.b_off = self->b_off;
   cfg.device = device;
   cfg.flags = HB2R_INVERSE (self) ? MIBAYER_FLAG_RGB2BAYER : 0;
-  self->ctx_mhc = !HB2R_INVERSE (self) && g_atomic_int_get (&self->method) == HB2R_METHOD_MHC;
-  if (self->ctx_mhc)
+  if (!HB2R_INVERSE (self) && g_atomic_int_get (&self->method) == HB2R_METHOD_MHC)
     cfg.flags |= MIBAYER_FLAG_MHC;
+  if (want_colour)
+    cfg.flags |= MIBAYER_FLAG_COLOUR;
+  self->ctx_single_shape = (cfg.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR)) != 0;
   rc = mibayer_create (&cfg, &self->ctx);
+  if (rc == MIBAYER_OK && want_colour && (rc = mibayer_set_colour (self->ctx, &colour)) != MIBAYER_OK) {
+    mibayer_destroy (self->ctx);
+    self->ctx = NULL;
+    GST_ELEMENT_ERROR (self, LIBRARY, SETTINGS,
+        ("%s: cannot set up the colour stage", HB2R_LABEL (self)),
+        ("mibayer_set_colour: %s", mibayer_strerror (rc)));
+    return FALSE;
+  }
   if (rc != MIBAYER_OK) {
     self->ctx = NULL;
     GST_ELEMENT_ERROR (self, RESOURCE, FAILED,
@@ -1180,7 +1226,7 @@ hb2r_autotune_once (GstMiHipBayer2RGB * self, const void *const *srcs,
   if (self->tuned)
     return;
   self->tuned = TRUE;           /* from here on the launches may leave the context's stream (hb2r_next_stream) */
-  if (HB2R_INVERSE (self) || self->ctx_mhc)
+  if (HB2R_INVERSE (self) || self->ctx_single_shape)
     return;                     /* rgb2bayer and MHC have one launch shape: nothing to measure */
   (void) mibayer_get_plan_for (self->ctx, (int) n, NULL, NULL, NULL, &src);
   if (src != MIBAYER_PLAN_DEFAULT)
@@ -1662,6 +1708,7 @@ gst_mi_hip_bayer2rgb_class_init (GstMiHipBayer2RGBClass * klass)
           "element; autotune has nothing to measure).  No effect on hiprgb2bayer",
           hb2r_method_get_type (), HB2R_METHOD_BILINEAR,
           G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY | G_PARAM_STATIC_STRINGS));
+  gst_mi_colour_install_properties (object_class, PROP_COLOUR_FIRST);
   xfer_add_templates (element_class, HB2R_SINK_CAPS, HB2R_SRC_CAPS);
   gst_element_class_set_static_metadata (element_class,
       "Bayer to RGB decoder (HIP device memory)", "Filter/Converter/Video",
@@ -1699,7 +1746,8 @@ gst_mi_hip_bayer2rgb_init (GstMiHipBayer2RGB * self)
   self->tuned = FALSE;
   self->plan[0] = '\0';
   self->method = HB2R_METHOD_BILINEAR;
-  self->ctx_mhc = FALSE;
+  self->ctx_single_shape = FALSE;
+  gst_mi_colour_props_init (&self->colour);
   self->prerolled = FALSE;
   g_queue_init (&self->waiting);
   g_queue_init (&self->ready);

@@ -64,6 +64,8 @@ extern "C" {
 /* 5, later additive: deep samples -- flags only (MIBAYER_FLAG_SRC_BITS, _SRC_BIG_ENDIAN, _DST_16BIT,
  * _DST_BIG_ENDIAN: 10-16-bit mosaics in 16-bit words, 16-bit-per-channel output); no struct field and no entry point
  * was added, and a cfg without them means what it meant.  Likewise MIBAYER_FLAG_MHC (Malvar-He-Cutler demosaic). */
+/* 5, later additive: the fused colour stage -- MIBAYER_FLAG_COLOUR, struct mibayer_colour and the entry points of
+ * group `colour`; a cfg without the flag means what it meant. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -98,6 +100,9 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group colour: the opt-in colour stage fused into the demosaic (MIBAYER_FLAG_COLOUR): black level, matrix, tone curve
+ *     mibayer_colour_init mibayer_set_colour mibayer_get_colour mibayer_pool_set_colour mibayer_colour_matrix
+ *     mibayer_colour_tone
  * END OF MIBAYER ABI GROUPS */
 
 /* Bayer order; numbering identical to the reference's anonymous enum
@@ -222,7 +227,65 @@ typedef struct mibayer_cfg {
  * mibayer_ctx_variant_name names the MHC kernel. */
 #define MIBAYER_FLAG_MHC (1u << 16)
 
+/* Fused colour stage (additive within version 5: a flag, a struct and the entry points of group `colour`).  What the
+ * demosaic leaves is sensor-space data; a COLOUR context subtracts the black level, applies a 3x3 matrix (white
+ * balance x colour correction) and optionally a tone curve inside the demosaic kernel, on the values it holds in
+ * registers -- no second pass over the frame.  depth = 8 or `bits`, max = 2^depth - 1, (R, G, B) = the demosaiced values
+ * at native depth, exactly what the deep or MHC path computes before its output conversion.  Per pixel, in integers:
+ *   1. c = max (c - black[k], 0)                                           k = R, G, B; black[k] in 0 .. 65535
+ *   2. acc_k = m[3k] R + m[3k+1] G + m[3k+2] B  (exact)                    Q12: 4096 = 1.0, entries in -65535 .. 65535
+ *      c'_k = clamp ((acc_k + 2048) >> 12, 0, max)                         arithmetic shift
+ *   3. with a tone curve (has_tone, tone[257], entries in 0 .. 65536):
+ *        t = c' << (16 - depth), i = t >> 8, f = t & 255
+ *        o = min ((tone[i] (256 - f) + tone[i+1] f + 128) >> 8, 65535)
+ *      16-bit channels take o, 8-bit channels o >> 8; without a curve the deep path's output conversion applies to c'
+ *   4. alpha, byte orders and the four layouts as without the flag.
+ * Zero black level, the identity matrix and no curve give the bytes of the same cfg without the flag; tone[i] = 256 i on
+ * top leaves 16-bit output unchanged.  The flag goes with every deep flag, with MIBAYER_FLAG_MHC and with
+ * MIBAYER_FLAG_HIPGRAPH (the host path runs without graphs); with MIBAYER_FLAG_RGB2BAYER or variant != 0 it is
+ * MIBAYER_ERR_ARG.  Geometry, strides and layouts are those of the same cfg without the flag.  Like a deep or MHC
+ * context a colour context has one kernel shape and no plans: mibayer_autotune[_list], mibayer_set_plan[_for],
+ * mibayer_plan_selectors and mibayer_launch_geometry return MIBAYER_ERR_ARG; mibayer_fill_synthetic works when the
+ * mosaic is 8-bit; mibayer_ctx_variant_name names the colour kernel. */
+#define MIBAYER_FLAG_COLOUR (1u << 19)
+
+typedef struct mibayer_colour {
+  uint32_t struct_size;         /* = sizeof (mibayer_colour) */
+  int32_t black[3];             /* R, G, B, at native depth */
+  int32_t matrix[9];            /* row-major, Q12: output channel k = row k */
+  int32_t has_tone;             /* 0 / 1 */
+  uint32_t tone[257];
+} mibayer_colour;
+
+#define MIBAYER_TONE_LINEAR 0   /* tone[i] = 256 i */
+#define MIBAYER_TONE_SRGB 1     /* the sRGB transfer function (IEC 61966-2-1) */
+#define MIBAYER_TONE_GAMMA 2    /* x ^ (1 / gamma), gamma in 0.01 .. 100 */
+
 typedef struct mibayer_ctx mibayer_ctx;
+typedef struct mibayer_pool mibayer_pool;
+
+/* the identity: zero black level, matrix 4096 on the diagonal, no tone curve */
+void mibayer_colour_init (mibayer_colour *colour);
+/* Sets / reads the stage of a COLOUR context (a new one holds the identity).  MIBAYER_ERR_ARG on a context without
+ * the flag and on out-of-range values.  May be called between frames, from any thread: it applies to the frames
+ * accepted (mibayer_submit / mibayer_process_host) and the device-path calls made after it returns, never to ones
+ * already queued.  A host-path frame takes ONE copy of the parameters when it is accepted, whatever number of bands
+ * it is launched in, a mibayer_process_device[_list] call one per call; the copy, tone table included, travels in the
+ * kernel arguments. */
+int mibayer_set_colour (mibayer_ctx *ctx, const mibayer_colour *colour);
+int mibayer_get_colour (const mibayer_ctx *ctx, mibayer_colour *out);
+/* ... of a pool: the stage of the frames mibayer_pool_submit accepts after it returns.  The pool keeps the stage with
+ * each frame and gives it to a shard's context only together with the frame, so frames that still wait in a shard's
+ * helper thread keep the parameters they were submitted with, and so does a frame that is converted again on a
+ * surviving device after a failover.  Call it from the thread that calls mibayer_pool_submit.  MIBAYER_ERR_ARG on a
+ * pool without the flag and on out-of-range values. */
+int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour *colour);
+/* Pure host helpers (no device needed), so that every caller rounds alike.  out = round (ccm x diag (gains) x 4096):
+ * white-balance gains per input channel (R, G, B) under a colour-correction matrix (NULL = identity);
+ * MIBAYER_ERR_ARG when an entry leaves -65535 .. 65535. */
+int mibayer_colour_matrix (const double gains[3], const double ccm[9], int32_t out[9]);
+/* tone[i] = round (65536 f (i / 256)) for MIBAYER_TONE_*; `gamma` is read by MIBAYER_TONE_GAMMA only */
+int mibayer_colour_tone (int curve, double gamma, uint32_t tone[257]);
 
 /* ---- global ------------------------------------------------------------- */
 
@@ -324,8 +387,6 @@ typedef struct mibayer_pool_cfg {
   int32_t ndevices;             /* 1 .. MIBAYER_MAX_SHARDS                      */
   int32_t devices[MIBAYER_MAX_SHARDS];  /* HIP ordinals                         */
 } mibayer_pool_cfg;
-
-typedef struct mibayer_pool mibayer_pool;
 
 int mibayer_pool_create (const mibayer_pool_cfg *cfg, mibayer_pool **out);
 void mibayer_pool_destroy (mibayer_pool *pool);
