@@ -295,9 +295,8 @@ struct mibayer_ctx {
   /* deep samples (MIBAYER_FLAG_SRC_BITS / _DST_16BIT ...): one kernel shape (bayer2rgb_deep_kernel), no plans; the
    * host path runs without graphs, as rgb2bayer does */
   bool deep = false;
-  bool deep_in8 = false;                /* 8-bit mosaic (16-bit output unless mhc) */
-  bool mhc = false;                     /* MIBAYER_FLAG_MHC: bayer2rgb_mhc_kernel; a deep context, 8-bit ones included */
-  bool deep_out16 = false;
+  StripKind kind = { false, false, false };     /* mhc: MIBAYER_FLAG_MHC, a deep context, 8-bit ones included; in8: 8-bit
+                                                   mosaic (16-bit output unless mhc or colour); out16 */
   /* MIBAYER_FLAG_COLOUR: bayer2rgb_colour_kernel, a deep context (8-bit ones included).  A host-path frame takes ONE
    * copy of the stage under the lock when it is accepted (Slot::stage), a device-path call one per call; the copy
    * travels in the kernel arguments, so mibayer_set_colour never touches what is already queued */
@@ -741,27 +740,27 @@ static void make_plan (mibayer_ctx *c)
   plan_selectors (c->cfg, c->sel, c->swap_rows);
 }
 
-/* Malvar-He-Cutler: the site map and output selectors (bayer2rgb_mhc_kernel, mibayer_kernels.hip).  A row's non-green
+/* Malvar-He-Cutler and the colour stage: the site map and output selectors (emit_cgd, mibayer_kernels.hip).  A row's non-green
  * colour C and the other one D: x = [C, G], y = [D, 0] at output depth, so v_perm bytes 4,5 = C, 6,7 = G, 0,1 = D,
  * 0x0d = 0xff (alpha).  4-byte output takes the low byte of each value, 16-bit output both, swapped for big-endian. */
-static void make_mhc_selectors (mibayer_ctx *c, int depth)
+static void make_cgd_selectors (mibayer_ctx *c, int depth)
 {
   const mibayer_cfg &f = c->cfg;
   DeepParams &q = c->deep_args;
   /* top-left 2x2 in raster order: bggr = B G / G R, gbrg = G B / R G, grbg = G R / B G, rggb = R G / G B */
-  q.mhc_green_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_RGGB;
-  q.mhc_red_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_GBRG;
-  q.mhc_max = (1 << depth) - 1;
+  q.green_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_RGGB;
+  q.red_odd = f.pattern == MIBAYER_BGGR || f.pattern == MIBAYER_GBRG;
+  q.vmax = (1 << depth) - 1;
   const bool be = (f.flags & MIBAYER_FLAG_DST_BIG_ENDIAN) != 0;
   for (int rk = 0; rk < 2; rk++) {
     const int r_lo = rk == 0 ? 4 : 0, b_lo = rk == 0 ? 0 : 4;  /* rk 0: C = R, D = B */
-    if (!c->deep_out16) {
+    if (!c->kind.out16) {
       uint32_t s = 0;
       for (int ch = 0; ch < 4; ch++) {
         const uint32_t b = ch == f.r_off ? r_lo : ch == f.b_off ? b_lo : ch == f.g_off ? 6 : 0x0d;
         s |= b << (8 * ch);
       }
-      q.mhc_sel[rk][0] = q.mhc_sel[rk][1] = s;
+      q.sel_cgd[rk][0] = q.sel_cgd[rk][1] = s;
       continue;
     }
     for (int d = 0; d < 2; d++) {
@@ -777,7 +776,7 @@ static void make_mhc_selectors (mibayer_ctx *c, int depth)
         }
         s |= (lo << (16 * slot)) | (hi << (16 * slot + 8));
       }
-      q.mhc_sel[rk][d] = s;
+      q.sel_cgd[rk][d] = s;
     }
   }
 }
@@ -791,8 +790,8 @@ static void make_deep_plan (mibayer_ctx *c)
   const mibayer_cfg &f = c->cfg;
   const uint32_t bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
   const int depth = bits ? (int) bits : 8;
-  c->deep_in8 = bits == 0;
-  c->deep_out16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
+  c->kind.in8 = bits == 0;
+  c->kind.out16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
   DeepParams &q = c->deep_args;
   q = DeepParams ();
   q.width = f.width;
@@ -803,9 +802,9 @@ static void make_deep_plan (mibayer_ctx *c)
   q.swap_rows = c->swap_rows;
   q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
   q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
-  q.out_shift = c->deep_out16 ? 16 - depth : depth - 8;
-  if (c->mhc || c->colour)
-    make_mhc_selectors (c, depth);
+  q.out_shift = c->kind.out16 ? 16 - depth : depth - 8;
+  if (c->kind.mhc || c->colour)
+    make_cgd_selectors (c, depth);
   for (int k = 0; k < 4; k++)
     q.sel[k] = c->sel[k];
   int rp = f.r_off, bp = f.b_off;
@@ -843,29 +842,26 @@ static void make_deep_plan (mibayer_ctx *c)
     }
 }
 
-/* one launch of the deep kernel: frames at q.src / q.dst + f * frame bytes or the q.nlist frames of q.src_list /
- * q.dst_list, all of them or chunks [chunk0, chunk0 + nchunks) of kDeepRows rows (host-path bands) */
 static void colour_snapshot (const mibayer_ctx *c, ColourStage *st)
 {
   std::lock_guard<std::mutex> lk (c->colour_mu);
   *st = c->colour_stage;
 }
 
-/* stage: the colour stage to launch with (a colour context); NULL = the context's current one */
+/* one launch of the context's strip kernel: frames at q.src / q.dst + f * frame bytes or the q.nlist frames of
+ * q.src_list / q.dst_list, all of them or chunks [chunk0, chunk0 + nchunks) of kStripRows rows (host-path bands).
+ * stage: the colour stage to launch with (a colour context); NULL = the context's current one */
 static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1, const ColourStage *stage = nullptr)
 {
-  if (c->colour) {
-    ColourStage now;
-    if (!stage) {
-      colour_snapshot (c, &now);
-      stage = &now;
-    }
-    HIP_TRY (launch_colour (q, *stage, c->mhc, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
-  } else if (c->mhc)
-    HIP_TRY (launch_mhc (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
-  else
-    HIP_TRY (launch_deep (q, c->deep_in8, c->deep_out16, nframes, stream, chunk0, nchunks));
+  ColourStage now;
+  if (!c->colour) {
+    stage = nullptr;
+  } else if (!stage) {
+    colour_snapshot (c, &now);
+    stage = &now;
+  }
+  HIP_TRY (launch_strip (q, c->kind, stage, nframes, stream, chunk0, nchunks));
   return MIBAYER_OK;
 }
 
@@ -1033,7 +1029,7 @@ static int launch (const mibayer_ctx *c, const void *d_src,
 {
   if (nframes == 0 || ntile_rows == 0)
     return MIBAYER_OK;
-  if (c->deep) {                /* tile rows = chunks of deep_rows (c) rows */
+  if (c->deep) {                /* tile rows = chunks of kStripRows rows */
     DeepParams q = c->deep_args;
     q.src = (const uint8_t *) d_src;
     q.dst = (uint8_t *) d_dst;
@@ -1393,13 +1389,13 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->src_bytes = (size_t) f.src_stride * f.height;
   c->dst_bytes = (size_t) f.dst_stride * f.height;
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
-  c->mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
+  c->kind.mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
   c->colour = (f.flags & MIBAYER_FLAG_COLOUR) != 0;
   if (c->colour) {
     mibayer_colour_init (&c->colour_user);
     (void) colour_stage_from (&c->colour_user, &c->colour_stage);
   }
-  c->deep = c->mhc || c->colour || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
+  c->deep = c->kind.mhc || c->colour || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1759,8 +1755,8 @@ extern "C" int mibayer_known_width_plan (int width, int *variant, int *band)
 extern "C" const char *mibayer_ctx_variant_name (const mibayer_ctx *c)
 {
   if (c && c->colour)
-    return c->mhc ? "colour_mhc_256x16" : "colour_bilinear_256x16";
-  if (c && c->mhc)
+    return c->kind.mhc ? "colour_mhc_256x16" : "colour_bilinear_256x16";
+  if (c && c->kind.mhc)
     return "mhc_256x16";
   return c ? c->plan[PLAN_BATCH].var->name : NULL;
 }
@@ -1937,11 +1933,6 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
  * gets most of what the queued mode gets from overlapping whole frames.
  * Bands are whole tile rows; the bottom-edge rule dn(H-1) = H-4
  * (gstbayer2rgb.c:430-447) needs the last band to hold at least 4 rows. */
-static int deep_rows (const mibayer_ctx *c)
-{
-  return c->mhc || c->colour ? kMhcRows : kDeepRows;
-}
-
 static int choose_host_bands (const mibayer_ctx *c)
 {
   int want = 4;
@@ -1954,7 +1945,7 @@ static int choose_host_bands (const mibayer_ctx *c)
       || big_side < ((size_t) 16 << 20))        /* below ~4K the extra enqueues cost more
                                                    than the overlap gains (1080p: -10 %) */
     return 1;
-  const int th = c->inverse ? kInverseBandUnit : c->deep ? deep_rows (c) : plan_for (c, 1).var->tile_h;
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? kStripRows : plan_for (c, 1).var->tile_h;
   const int tiles_y = (c->cfg.height + th - 1) / th;
   while (want > 1) {
     const int per = (tiles_y + want - 1) / want;        /* tile rows per band */
@@ -1971,9 +1962,9 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     uint8_t *dst, size_t row_bytes)
 {
   const mibayer_cfg &f = c->cfg;
-  const int th = c->inverse ? kInverseBandUnit : c->deep ? deep_rows (c) : plan_for (c, 1).var->tile_h;
+  const int th = c->inverse ? kInverseBandUnit : c->deep ? kStripRows : plan_for (c, 1).var->tile_h;
   /* rgb2bayer has no neighbourhood, MHC's is 5x5, and the colour kernel loads the MHC window whatever the method */
-  const int halo = c->inverse ? 0 : c->mhc || c->colour ? 2 : 1;
+  const int halo = c->inverse ? 0 : c->kind.mhc || c->colour ? 2 : 1;
   const int tiles_y = (f.height + th - 1) / th;
   const int nb = c->host_bands;
   const int per = (tiles_y + nb - 1) / nb;
@@ -2137,7 +2128,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 static size_t written_row_bytes (const mibayer_ctx *c)
 {
   return c->inverse ? (size_t) ((c->cfg.width + 3) & ~3)
-      : (size_t) (c->deep_out16 ? 8 : 4) * c->cfg.width;
+      : (size_t) (c->kind.out16 ? 8 : 4) * c->cfg.width;
 }
 
 static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
@@ -3450,7 +3441,7 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     void *hip_stream)
 {
   /* the generator writes 8-bit mosaics: an MHC context of one takes it, no other deep context does */
-  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !((c->mhc || c->colour) && c->deep_in8)))
+  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !((c->kind.mhc || c->colour) && c->kind.in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

@@ -231,9 +231,10 @@ hipError_t launch_rgb2bayer (const R2BParams &p, bool vec16, hipStream_t stream,
  * kernel (p.flat_k > 0); dst8: every destination 8-byte aligned (two items per store allowed) */
 hipError_t launch_rgb2bayer_list (const R2BParams &p, bool vec16, bool dst8, hipStream_t stream);
 
-/* bayer2rgb on deep samples (MIBAYER_FLAG_SRC_BITS / MIBAYER_FLAG_DST_16BIT): 16-bit-word mosaics of 10-16 significant
- * bits, and/or 16-bit-per-channel output.  One wave owns a strip of 256 pixels x kDeepRows rows ("chunk") */
-constexpr int kDeepRows = 16;
+/* The strip kernels.  bayer2rgb on deep samples (MIBAYER_FLAG_SRC_BITS / MIBAYER_FLAG_DST_16BIT): 16-bit-word mosaics
+ * of 10-16 significant bits, and/or 16-bit-per-channel output; Malvar-He-Cutler (MIBAYER_FLAG_MHC) and the fused colour
+ * stage (MIBAYER_FLAG_COLOUR) on the same arguments.  One wave owns a strip of 256 pixels x kStripRows rows ("chunk") */
+constexpr int kStripRows = 16;
 struct DeepParams {
   const uint8_t *src;
   uint8_t *dst;
@@ -250,13 +251,13 @@ struct DeepParams {
   int out_shift;                /* 16-bit out: left shift (16 - bits); 8-bit out: right shift (bits - 8) */
   uint32_t sel[4];              /* 8-bit out: v_perm selectors of output pixel k (mibayer_plan_selectors) */
   uint32_t sel16[2][2];         /* 16-bit out: [pixel parity][dword of the pixel], over {R'B' word, G word} */
-  /* MIBAYER_FLAG_MHC (bayer2rgb_mhc_kernel) */
-  int mhc_green_odd;            /* green sites of row 0 are at odd columns (bggr, rggb) */
-  int mhc_red_odd;              /* red sites are in odd rows (bggr, gbrg) */
-  int mhc_max;                  /* 2^depth - 1 */
-  uint32_t mhc_sel[2][2];       /* [row: 0 = its non-green colour is R, 1 = B][output dword], v_perm selectors over
+  /* the site map and the values' range: bayer2rgb_mhc_kernel and both arms of bayer2rgb_colour_kernel */
+  int green_odd;                /* green sites of row 0 are at odd columns (bggr, rggb) */
+  int red_odd;                  /* red sites are in odd rows (bggr, gbrg) */
+  int vmax;                     /* 2^depth - 1 */
+  uint32_t sel_cgd[2][2];       /* [row: 0 = its non-green colour is R, 1 = B][output dword], v_perm selectors over
                                    {x = [C, G], y = [D, 0]} at output depth; 4-byte output uses [.][0] only */
-  /* filled by launch_deep */
+  /* filled by launch_strip */
   int groups;                   /* 4-pixel groups per row = ceil (width / 4) */
   FastDiv div_tiles_x;          /* 256-pixel strips per row */
   FastDiv div_chunks;           /* chunks per frame */
@@ -266,17 +267,6 @@ struct DeepParams {
   const uint8_t *src_list[kMaxList];
   uint8_t *dst_list[kMaxList];
 };
-/* in8: 8-bit mosaic (then out16 is set); out16: 8-byte output pixels.  Chunks [chunk0, chunk0 + nchunks) of the batch
- * (nchunks < 0: all of p.nlist frames, or of `nframes`) */
-hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
-    long long chunk0 = 0, long long nchunks = -1);
-
-/* Malvar-He-Cutler demosaic (MIBAYER_FLAG_MHC) on the deep kernel's arguments: in8 = 8-bit mosaic, out16 = 8-byte
- * output pixels, all four combinations.  Chunks of kMhcRows rows, otherwise as launch_deep */
-constexpr int kMhcRows = 16;
-hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
-    long long chunk0 = 0, long long nchunks = -1);
-
 /* Fused colour stage (MIBAYER_FLAG_COLOUR, bayer2rgb_colour_kernel): black level, Q12 matrix, tone curve on the
  * demosaiced native-depth values, before the output conversion.  The matrix entry m is split as m = hi * 4096 + lo
  * (hi = m >> 12 in [-16, 15], lo = m & 4095): sum (m v) = 4096 * sum (hi v) + sum (lo v) with v <= 65535, so both sums
@@ -295,10 +285,15 @@ struct ColourParams {
   int in8, out16;
   ColourStage s;
 };
-/* one kernel for both demosaic methods and all four input / output combinations (uniform run-time branches); chunks of
- * kMhcRows rows, otherwise as launch_mhc */
-hipError_t launch_colour (const DeepParams &p, const ColourStage &s, bool mhc, bool in8, bool out16, int nframes,
-    hipStream_t stream, long long chunk0 = 0, long long nchunks = -1);
+/* which strip kernel: Malvar-He-Cutler or the bilinear closed form, 8-bit mosaic or 16-bit words, 8- or 4-byte output
+ * pixels */
+struct StripKind { bool mhc, in8, out16; };
+/* One launch of a strip kernel over chunks [chunk0, chunk0 + nchunks) of the batch (nchunks < 0: all of p.nlist frames,
+ * or of `nframes`).  stage = NULL: bayer2rgb_deep_kernel / bayer2rgb_mhc_kernel of the kind; bilinear 8-bit mosaic to
+ * 4-byte pixels is refused (the production kernels serve it).  Otherwise bayer2rgb_colour_kernel with that stage: one
+ * kernel for both demosaic methods and all four input / output combinations (uniform run-time branches) */
+hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,
+    long long chunk0 = 0, long long nchunks = -1);
 
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);

@@ -1483,7 +1483,7 @@ hipError_t launch_rgb2bayer_list (const R2BParams &p, bool vec16, bool dst8, hip
  * 8-bit channels v >> (bits - 8) (alpha 255).  An 8-bit mosaic with 16-bit output is bits = 8.
  *
  * A lane owns 4 horizontally adjacent pixels as two dwords of two 16-bit samples each (lo = pixels 0,1, hi = 2,3), a
- * wave a strip of 256 pixels x kDeepRows rows: it loads all kDeepRows + 2 source rows first (the loads of a lane are all
+ * wave a strip of 256 pixels x kStripRows rows: it loads all kStripRows + 2 source rows first (the loads of a lane are all
  * in flight at once), then walks down with the 3-row window (E,O of rows u, j, d) in registers.  Two samples per dword: avg is exact per half without packed
  * instructions ((a|b) - (((a^b) >> 1) & 0x7fff7fff): no borrow crosses the halves), the output shift cannot cross
  * them either.  The x-1 / x+4 neighbours come from the adjacent lanes by DPP; lanes 0 and 63 load theirs.  Output
@@ -1592,6 +1592,40 @@ __device__ __forceinline__ void deep_quad_pieces (u32x4 v0, u32x4 v1, int k, u32
   s1 = (k & 1) ? h1 : h0;
 }
 
+/* 4-byte pixels of group g: four as one streaming 16-byte store, the two of a width % 4 == 2 tail (!full) as 8 bytes;
+ * store = the group is inside the row */
+__device__ __forceinline__ void store_strip8 (uint8_t *out, int g, bool store, bool full, u32x4 v)
+{
+  if (store) {
+    uint8_t *q = out + 16 * (size_t) g;
+    if (full) {
+      __builtin_nontemporal_store (v, (u32x4_a4 *) q);
+    } else {
+      const u32x2_a4 two = { v.x, v.y };
+      __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+    }
+  }
+}
+
+/* 8-byte pixels of group g: v0 = pixels 0,1 and v1 = pixels 2,3.  A lane holds 32 contiguous bytes, so two stores
+ * straight from its registers would each fill every other 16 bytes of the wave's 2 KiB.  The four lanes of a quad swap
+ * pieces instead (DPP quad_perm): the first store writes the quad's first 64 bytes, the second its last 64, and
+ * write-back stores let the L2 join the two halves of a 128-byte line.  4K x 16, 12-bit -> ARGB64: 30 % of peak with
+ * streaming stores straight from the registers, 47 % write-back, 41 % swapped + streaming, 50 % swapped + write-back.
+ * Every lane of the wave calls this: the DPP moves read lanes whose own group may lie past the row. */
+__device__ __forceinline__ void store_strip16 (const DeepParams &p, uint8_t *out, int g, int lane, u32x4 v0, u32x4 v1)
+{
+  const int k = lane & 3;
+  u32x4 s0, s1;
+  deep_quad_pieces (v0, v1, k, s0, s1);
+  const int qg = g - k;                                 /* first group of the quad */
+  const int ga = qg + (k >> 1), gb = qg + 2 + (k >> 1); /* group whose piece k&1 this lane stores */
+  if (ga < p.groups && ((k & 1) == 0 || 4 * ga + 4 <= p.width))
+    *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * k) = s0;
+  if (gb < p.groups && ((k & 1) == 0 || 4 * gb + 4 <= p.width))
+    *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * k) = s1;
+}
+
 template <bool IN8, bool OUT16>
 __global__ void __launch_bounds__ (256)
 bayer2rgb_deep_kernel (DeepParams p)
@@ -1604,8 +1638,8 @@ bayer2rgb_deep_kernel (DeepParams p)
   const uint32_t tx = wave - crow * p.div_tiles_x.d;
   const uint32_t chunk = p.chunk0 + crow;
   const uint32_t frame = fastdiv (chunk, p.div_chunks);
-  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kDeepRows;
-  const int y1 = y0 + kDeepRows < p.height ? y0 + kDeepRows : p.height;
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kStripRows;
+  const int y1 = y0 + kStripRows < p.height ? y0 + kStripRows : p.height;
   const uint8_t *src = p.nlist
       ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
   uint8_t *dst = p.nlist
@@ -1616,18 +1650,18 @@ bayer2rgb_deep_kernel (DeepParams p)
   const bool store = g < p.groups;
   const bool full = 4 * g + 4 <= p.width;
 
-  /* every source row of the chunk is loaded up front (kDeepRows + 2 loads in flight per lane): raw[0] = up(y0),
+  /* every source row of the chunk is loaded up front (kStripRows + 2 loads in flight per lane): raw[0] = up(y0),
    * raw[1 + k] = row y0 + k, and the row past the frame is dn(H-1) (rows past a short last chunk are never used) */
-  DeepRaw raw[kDeepRows + 2];
+  DeepRaw raw[kStripRows + 2];
 #pragma unroll
-  for (int i = 0; i < kDeepRows + 2; i++) {
+  for (int i = 0; i < kStripRows + 2; i++) {
     const int r = i == 0 ? (y0 == 0 ? 1 : y0 - 1) : y0 + i - 1;
     raw[i] = deep_load<IN8> (p, src, r < p.height ? r : p.dn_last, g, lane);
   }
   DeepLines up = deep_lines<IN8> (p, raw[0], lane, first, lastmode);
   DeepLines cur = deep_lines<IN8> (p, raw[1], lane, first, lastmode);
 #pragma unroll
-  for (int k = 0; k < kDeepRows; k++) {
+  for (int k = 0; k < kStripRows; k++) {
     const int j = y0 + k;
     if (j >= y1)
       break;
@@ -1670,20 +1704,7 @@ bayer2rgb_deep_kernel (DeepParams p)
       v1.y = __builtin_amdgcn_perm (m2, g_hi, p.sel16[0][1]);
       v1.z = __builtin_amdgcn_perm (m3, g_hi, p.sel16[1][0]);
       v1.w = __builtin_amdgcn_perm (m3, g_hi, p.sel16[1][1]);
-      /* A lane holds 32 contiguous bytes, so two stores straight from its registers would each fill every other
-       * 16 bytes of the wave's 2 KiB.  The four lanes of a quad swap pieces instead (DPP quad_perm): the first store
-       * writes the quad's first 64 bytes, the second its last 64, and write-back stores let the L2 join the two
-       * halves of a 128-byte line.  4K x 16, 12-bit -> ARGB64: 30 % of peak with streaming stores straight from the
-       * registers, 47 % write-back, 41 % swapped + streaming, 50 % swapped + write-back. */
-      const int k = lane & 3;
-      u32x4 s0, s1;
-      deep_quad_pieces (v0, v1, k, s0, s1);
-      const int qg = g - k;                             /* first group of the quad */
-      const int ga = qg + (k >> 1), gb = qg + 2 + (k >> 1);     /* group whose piece k&1 this lane stores */
-      if (ga < p.groups && ((k & 1) == 0 || 4 * ga + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * k) = s0;
-      if (gb < p.groups && ((k & 1) == 0 || 4 * gb + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * k) = s1;
+      store_strip16 (p, out, g, lane, v0, v1);
     } else {
       const int s = p.out_shift;
       constexpr uint32_t kLowBytes = 0x00ff00ffu;
@@ -1699,69 +1720,11 @@ bayer2rgb_deep_kernel (DeepParams p)
       v.y = __builtin_amdgcn_perm (m_lo, gw, p.sel[1]);
       v.z = __builtin_amdgcn_perm (m_hi, gw, p.sel[2]);
       v.w = __builtin_amdgcn_perm (m_hi, gw, p.sel[3]);
-      if (store) {
-        uint8_t *q = out + 16 * (size_t) g;
-        if (full) {
-          __builtin_nontemporal_store (v, (u32x4_a4 *) q);
-        } else {
-          const u32x2_a4 two = { v.x, v.y };
-          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
-        }
-      }
+      store_strip8 (out, g, store, full, v);
     }
     up = cur;
     cur = dn;
   }
-}
-
-/* the launch-dependent fields of q (strips of 256 pixels x `rows`-row chunks, chunks [chunk0, chunk0 + nchunks) of the
- * batch, nchunks < 0: all) and the grid; *grid = 0: nothing to launch */
-static hipError_t deep_grid (DeepParams &q, int rows, int nframes, long long chunk0, long long nchunks, unsigned *grid)
-{
-  *grid = 0;
-  q.groups = (q.width + 3) / 4;
-  const int tiles_x = (q.groups + 63) / 64;
-  const long long chunks_per_frame = (q.height + rows - 1) / rows;
-  const long long frames = q.nlist > 0 ? q.nlist : nframes;
-  if (q.nlist > kMaxList || frames <= 0)
-    return frames == 0 ? hipSuccess : hipErrorInvalidValue;
-  const long long total = frames * chunks_per_frame;
-  if (nchunks < 0) {
-    chunk0 = 0;
-    nchunks = total;
-  }
-  if (chunk0 < 0 || chunk0 + nchunks > total)
-    return hipErrorInvalidValue;
-  if (nchunks == 0)
-    return hipSuccess;
-  const long long waves = nchunks * tiles_x;
-  if (total > 0x7fffffffLL || waves > 0x7fffffffLL)
-    return hipErrorInvalidValue;
-  q.div_tiles_x = make_fastdiv ((uint32_t) tiles_x);
-  q.div_chunks = make_fastdiv ((uint32_t) chunks_per_frame);
-  q.chunk0 = (uint32_t) chunk0;
-  q.nwaves = (uint32_t) waves;
-  *grid = (unsigned) ((waves + 3) / 4);
-  return hipSuccess;
-}
-
-hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
-    long long chunk0, long long nchunks)
-{
-  if (p.width < 4 || p.height < 3 || (p.width & 1) || (in8 && !out16))
-    return hipErrorInvalidValue;
-  DeepParams q = p;
-  unsigned grid = 0;
-  const hipError_t e = deep_grid (q, kDeepRows, nframes, chunk0, nchunks, &grid);
-  if (e != hipSuccess || grid == 0)
-    return e;
-  if (in8)
-    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<true, true>), dim3 (grid), dim3 (256), 0, stream, q);
-  else if (out16)
-    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, true>), dim3 (grid), dim3 (256), 0, stream, q);
-  else
-    hipLaunchKernelGGL ((bayer2rgb_deep_kernel<false, false>), dim3 (grid), dim3 (256), 0, stream, q);
-  return hipGetLastError ();
 }
 
 /* ------------------------------------------------------------------------- */
@@ -1777,10 +1740,10 @@ hipError_t launch_deep (const DeepParams &p, bool in8, bool out16, int nframes, 
  *   B at R / R at B             F_diag = 12c + 4d - 3(h2 + v2)
  * Per row the non-green site colour is C (R in a red row, B in a blue one) and the other one D: a non-green site is
  * C = S, G = F_G, D = F_diag; a green site G = S, C = F_row, D = F_col.  Which of C / D is R is a property of the row,
- * so it only picks the output selectors (DeepParams::mhc_sel).  Samples and output conversion are the deep path's.
+ * so it only picks the output selectors (DeepParams::sel_cgd).  Samples and output conversion are the deep path's.
  *
- * Shape: the deep kernel's.  A lane owns 4 pixels, a wave a strip of 256 pixels x kMhcRows rows; it loads all
- * kMhcRows + 4 source rows first, then walks down with a 5-row window of unpacked rows in registers.  Columns x0-2,
+ * Shape: the deep kernel's.  A lane owns 4 pixels, a wave a strip of 256 pixels x kStripRows rows; it loads all
+ * kStripRows + 4 source rows first, then walks down with a 5-row window of unpacked rows in registers.  Columns x0-2,
  * x0-1 and x0+4, x0+5 come from the adjacent lanes by DPP (lanes 0 and 63 load their own edge dword), the border
  * columns are reflected in the lanes that hold them. */
 
@@ -1850,13 +1813,45 @@ __device__ __forceinline__ void mhc_pixel (const DeepParams &p, const MhcRow &m2
     f1 = 8 * c + 4 * (h1 + v1) - 2 * (h2 + v2);         /* G = F_G */
     f2 = 12 * c + 4 * d - 3 * (h2 + v2);                /* D = F_diag */
   }
-  f1 = min (max ((f1 + 8) >> 4, 0), p.mhc_max);      /* v_med3_i32 */
-  f2 = min (max ((f2 + 8) >> 4, 0), p.mhc_max);
+  f1 = min (max ((f1 + 8) >> 4, 0), p.vmax);         /* v_med3_i32 */
+  f2 = min (max ((f2 + 8) >> 4, 0), p.vmax);
   if constexpr (GREEN)
     C = f1;
   else
     G = f1;
   D = f2;
+}
+
+/* reflect-101 row index of a frame of `height` rows (-1 -> 1, -2 -> 2, H -> H-2, H+1 -> H-3); rows further out are
+ * never used and map to H-1 */
+__device__ __forceinline__ int reflect_row (int r, int height)
+{
+  r = r < 0 ? -r : r;
+  return r > height + 1 ? height - 1 : r >= height ? 2 * height - 2 - r : r;
+}
+
+/* {x = [C, G], y = [D, 0]} of the lane's four pixels at output depth -> output pixels by v_perm_b32 with the selectors
+ * s0, s1 (DeepParams::sel_cgd): 8-byte pixels v0 = pixels 0,1 and v1 = pixels 2,3 (s0 / s1 = the two dwords of a
+ * pixel), 4-byte pixels v0 = all four (s0 only, v1 is not written) */
+template <bool OUT16>
+__device__ __forceinline__ void emit_cgd (const uint32_t (&x)[4], const uint32_t (&y)[4], uint32_t s0, uint32_t s1,
+    u32x4 &v0, u32x4 &v1)
+{
+  if constexpr (OUT16) {
+    v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+    v0.y = __builtin_amdgcn_perm (x[0], y[0], s1);
+    v0.z = __builtin_amdgcn_perm (x[1], y[1], s0);
+    v0.w = __builtin_amdgcn_perm (x[1], y[1], s1);
+    v1.x = __builtin_amdgcn_perm (x[2], y[2], s0);
+    v1.y = __builtin_amdgcn_perm (x[2], y[2], s1);
+    v1.z = __builtin_amdgcn_perm (x[3], y[3], s0);
+    v1.w = __builtin_amdgcn_perm (x[3], y[3], s1);
+  } else {
+    v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
+    v0.y = __builtin_amdgcn_perm (x[1], y[1], s0);
+    v0.z = __builtin_amdgcn_perm (x[2], y[2], s0);
+    v0.w = __builtin_amdgcn_perm (x[3], y[3], s0);
+  }
 }
 
 template <bool IN8, bool OUT16>
@@ -1871,8 +1866,8 @@ bayer2rgb_mhc_kernel (DeepParams p)
   const uint32_t tx = wave - crow * p.div_tiles_x.d;
   const uint32_t chunk = p.chunk0 + crow;
   const uint32_t frame = fastdiv (chunk, p.div_chunks);
-  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kMhcRows;
-  const int y1 = y0 + kMhcRows < p.height ? y0 + kMhcRows : p.height;
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kStripRows;
+  const int y1 = y0 + kStripRows < p.height ? y0 + kStripRows : p.height;
   const uint8_t *src = p.nlist
       ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
   uint8_t *dst = p.nlist
@@ -1884,26 +1879,22 @@ bayer2rgb_mhc_kernel (DeepParams p)
   const bool full = 4 * g + 4 <= p.width;
 
   /* raw[i] = row y0 - 2 + i, reflected; rows past y1 + 1 (a short last chunk) are never used and read row H-1 */
-  DeepRaw raw[kMhcRows + 4];
+  DeepRaw raw[kStripRows + 4];
 #pragma unroll
-  for (int i = 0; i < kMhcRows + 4; i++) {
-    int r = y0 - 2 + i;
-    r = r < 0 ? -r : r;
-    r = r > p.height + 1 ? p.height - 1 : r >= p.height ? 2 * p.height - 2 - r : r;
-    raw[i] = deep_load<IN8> (p, src, r, g, lane);
-  }
+  for (int i = 0; i < kStripRows + 4; i++)
+    raw[i] = deep_load<IN8> (p, src, reflect_row (y0 - 2 + i, p.height), g, lane);
   MhcRow w0 = mhc_row<IN8> (p, raw[0], lane, first, lastmode);
   MhcRow w1 = mhc_row<IN8> (p, raw[1], lane, first, lastmode);
   MhcRow w2 = mhc_row<IN8> (p, raw[2], lane, first, lastmode);
   MhcRow w3 = mhc_row<IN8> (p, raw[3], lane, first, lastmode);
 #pragma unroll
-  for (int k = 0; k < kMhcRows; k++) {
+  for (int k = 0; k < kStripRows; k++) {
     const int j = y0 + k;
     if (j >= y1)
       break;
     const MhcRow w4 = mhc_row<IN8> (p, raw[k + 4], lane, first, lastmode);
     int C[4], G[4], D[4];
-    if (((j & 1) ^ p.mhc_green_odd) == 0) {             /* green at even columns (x0 is even) */
+    if (((j & 1) ^ p.green_odd) == 0) {             /* green at even columns (x0 is even) */
       mhc_pixel<true> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
       mhc_pixel<false> (p, w0, w1, w2, w3, w4, 1, C[1], G[1], D[1]);
       mhc_pixel<true> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
@@ -1914,7 +1905,7 @@ bayer2rgb_mhc_kernel (DeepParams p)
       mhc_pixel<false> (p, w0, w1, w2, w3, w4, 2, C[2], G[2], D[2]);
       mhc_pixel<true> (p, w0, w1, w2, w3, w4, 3, C[3], G[3], D[3]);
     }
-    const int rk = (j & 1) ^ p.mhc_red_odd;             /* 0: C is R (red row), 1: C is B */
+    const int rk = (j & 1) ^ p.red_odd;             /* 0: C is R (red row), 1: C is B */
     const int s = p.out_shift;
     uint32_t x[4], y[4];                                /* x = [C, G], y = [D, 0] at output depth */
 #pragma unroll
@@ -1929,69 +1920,21 @@ bayer2rgb_mhc_kernel (DeepParams p)
     }
     uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
     if constexpr (OUT16) {
-      const uint32_t s0 = p.mhc_sel[rk][0], s1 = p.mhc_sel[rk][1];
+      const uint32_t s0 = p.sel_cgd[rk][0], s1 = p.sel_cgd[rk][1];
       u32x4 v0, v1;
-      v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
-      v0.y = __builtin_amdgcn_perm (x[0], y[0], s1);
-      v0.z = __builtin_amdgcn_perm (x[1], y[1], s0);
-      v0.w = __builtin_amdgcn_perm (x[1], y[1], s1);
-      v1.x = __builtin_amdgcn_perm (x[2], y[2], s0);
-      v1.y = __builtin_amdgcn_perm (x[2], y[2], s1);
-      v1.z = __builtin_amdgcn_perm (x[3], y[3], s0);
-      v1.w = __builtin_amdgcn_perm (x[3], y[3], s1);
-      /* the deep kernel's store: the lanes of a quad swap pieces so that each store writes 64 contiguous bytes */
-      const int kq = lane & 3;
-      u32x4 s0v, s1v;
-      deep_quad_pieces (v0, v1, kq, s0v, s1v);
-      const int qg = g - kq;
-      const int ga = qg + (kq >> 1), gb = qg + 2 + (kq >> 1);
-      if (ga < p.groups && ((kq & 1) == 0 || 4 * ga + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * kq) = s0v;
-      if (gb < p.groups && ((kq & 1) == 0 || 4 * gb + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * kq) = s1v;
+      emit_cgd<true> (x, y, s0, s1, v0, v1);
+      store_strip16 (p, out, g, lane, v0, v1);
     } else {
-      const uint32_t s0 = p.mhc_sel[rk][0];
-      u32x4 v;
-      v.x = __builtin_amdgcn_perm (x[0], y[0], s0);
-      v.y = __builtin_amdgcn_perm (x[1], y[1], s0);
-      v.z = __builtin_amdgcn_perm (x[2], y[2], s0);
-      v.w = __builtin_amdgcn_perm (x[3], y[3], s0);
-      if (store) {
-        uint8_t *q = out + 16 * (size_t) g;
-        if (full) {
-          __builtin_nontemporal_store (v, (u32x4_a4 *) q);
-        } else {
-          const u32x2_a4 two = { v.x, v.y };
-          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
-        }
-      }
+      const uint32_t s0 = p.sel_cgd[rk][0];
+      u32x4 v, unused;
+      emit_cgd<false> (x, y, s0, s0, v, unused);
+      store_strip8 (out, g, store, full, v);
     }
     w0 = w1;
     w1 = w2;
     w2 = w3;
     w3 = w4;
   }
-}
-
-hipError_t launch_mhc (const DeepParams &p, bool in8, bool out16, int nframes, hipStream_t stream,
-    long long chunk0, long long nchunks)
-{
-  if (p.width < 4 || p.height < 3 || (p.width & 1))
-    return hipErrorInvalidValue;
-  DeepParams q = p;
-  unsigned grid = 0;
-  const hipError_t e = deep_grid (q, kMhcRows, nframes, chunk0, nchunks, &grid);
-  if (e != hipSuccess || grid == 0)
-    return e;
-  if (in8 && out16)
-    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<true, true>), dim3 (grid), dim3 (256), 0, stream, q);
-  else if (in8)
-    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<true, false>), dim3 (grid), dim3 (256), 0, stream, q);
-  else if (out16)
-    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<false, true>), dim3 (grid), dim3 (256), 0, stream, q);
-  else
-    hipLaunchKernelGGL ((bayer2rgb_mhc_kernel<false, false>), dim3 (grid), dim3 (256), 0, stream, q);
-  return hipGetLastError ();
 }
 
 /* ------------------------------------------------------------------------- */
@@ -2018,11 +1961,12 @@ constexpr int kColourAhead = 4;
 __device__ __forceinline__ DeepRaw colour_load (const ColourParams &cp, const uint8_t *src, int r, int g, int lane)
 {
   const DeepParams &p = cp.d;
-  r = r < 0 ? -r : r;
-  if (cp.mhc)
-    r = r > p.height + 1 ? p.height - 1 : r >= p.height ? 2 * p.height - 2 - r : r;
-  else
+  if (cp.mhc) {
+    r = reflect_row (r, p.height);
+  } else {
+    r = r < 0 ? -r : r;
     r = r == p.height ? p.dn_last : r > p.height ? p.height - 1 : r;
+  }
   if (cp.in8)
     return deep_load<true> (p, src, r, g, lane);
   return deep_load<false> (p, src, r, g, lane);
@@ -2091,8 +2035,8 @@ bayer2rgb_colour_kernel (ColourParams cp)
   const uint32_t tx = wave - crow * p.div_tiles_x.d;
   const uint32_t chunk = p.chunk0 + crow;
   const uint32_t frame = fastdiv (chunk, p.div_chunks);
-  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kMhcRows;
-  const int y1 = y0 + kMhcRows < p.height ? y0 + kMhcRows : p.height;
+  const int y0 = (int) (chunk - frame * p.div_chunks.d) * kStripRows;
+  const int y1 = y0 + kStripRows < p.height ? y0 + kStripRows : p.height;
   const uint8_t *src = p.nlist
       ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
   uint8_t *dst = p.nlist
@@ -2130,7 +2074,7 @@ bayer2rgb_colour_kernel (ColourParams cp)
     if (j + 2 + kColourAhead <= y1 + 1)                 /* the last output row, y1 - 1, needs row y1 + 1 */
       ring[kColourAhead - 1] = colour_load (cp, src, j + 2 + kColourAhead, g, lane);
     int C[4], G[4], D[4];
-    const bool green_even = ((j & 1) ^ p.mhc_green_odd) == 0;
+    const bool green_even = ((j & 1) ^ p.green_odd) == 0;
     if (cp.mhc) {
       if (green_even) {
         mhc_pixel<true> (p, w0, w1, w2, w3, w4, 0, C[0], G[0], D[0]);
@@ -2155,7 +2099,7 @@ bayer2rgb_colour_kernel (ColourParams cp)
       bilinear_pixel<true> (w1, w2, w3, 3, C[3], G[3], D[3]);
     }
     /* the colour stage: (R, G, B) -> black level -> matrix -> clamp, 24-bit multiplies on the split entries */
-    const bool c_is_red = ((j & 1) ^ p.mhc_red_odd) == 0;
+    const bool c_is_red = ((j & 1) ^ p.red_odd) == 0;
     int v[4][3];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -2169,7 +2113,7 @@ bayer2rgb_colour_kernel (ColourParams cp)
         const uint32_t lo = __umul24 ((uint32_t) cp.s.m_lo[3 * ch], (uint32_t) r)
             + __umul24 ((uint32_t) cp.s.m_lo[3 * ch + 1], (uint32_t) gr)
             + __umul24 ((uint32_t) cp.s.m_lo[3 * ch + 2], (uint32_t) b);
-        v[i][ch] = min (max (hi + (int) ((lo + 2048u) >> 12), 0), p.mhc_max);
+        v[i][ch] = min (max (hi + (int) ((lo + 2048u) >> 12), 0), p.vmax);
       }
     }
     uint32_t o[4][3];
@@ -2198,41 +2142,15 @@ bayer2rgb_colour_kernel (ColourParams cp)
       y[i] = o[i][2];
     }
     uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
-    const uint32_t s0 = p.mhc_sel[0][0], s1 = p.mhc_sel[0][1];
+    const uint32_t s0 = p.sel_cgd[0][0], s1 = p.sel_cgd[0][1];
     if (cp.out16) {
       u32x4 v0, v1;
-      v0.x = __builtin_amdgcn_perm (x[0], y[0], s0);
-      v0.y = __builtin_amdgcn_perm (x[0], y[0], s1);
-      v0.z = __builtin_amdgcn_perm (x[1], y[1], s0);
-      v0.w = __builtin_amdgcn_perm (x[1], y[1], s1);
-      v1.x = __builtin_amdgcn_perm (x[2], y[2], s0);
-      v1.y = __builtin_amdgcn_perm (x[2], y[2], s1);
-      v1.z = __builtin_amdgcn_perm (x[3], y[3], s0);
-      v1.w = __builtin_amdgcn_perm (x[3], y[3], s1);
-      const int kq = lane & 3;
-      u32x4 s0v, s1v;
-      deep_quad_pieces (v0, v1, kq, s0v, s1v);
-      const int qg = g - kq;
-      const int ga = qg + (kq >> 1), gb = qg + 2 + (kq >> 1);
-      if (ga < p.groups && ((kq & 1) == 0 || 4 * ga + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 16 * kq) = s0v;
-      if (gb < p.groups && ((kq & 1) == 0 || 4 * gb + 4 <= p.width))
-        *(u32x4_a4 *) (out + 32 * (size_t) qg + 64 + 16 * kq) = s1v;
+      emit_cgd<true> (x, y, s0, s1, v0, v1);
+      store_strip16 (p, out, g, lane, v0, v1);
     } else {
-      u32x4 vv;
-      vv.x = __builtin_amdgcn_perm (x[0], y[0], s0);
-      vv.y = __builtin_amdgcn_perm (x[1], y[1], s0);
-      vv.z = __builtin_amdgcn_perm (x[2], y[2], s0);
-      vv.w = __builtin_amdgcn_perm (x[3], y[3], s0);
-      if (store) {
-        uint8_t *q = out + 16 * (size_t) g;
-        if (full) {
-          __builtin_nontemporal_store (vv, (u32x4_a4 *) q);
-        } else {
-          const u32x2_a4 two = { vv.x, vv.y };
-          __builtin_nontemporal_store (two, (u32x2_a4 *) q);
-        }
-      }
+      u32x4 vv, unused;
+      emit_cgd<false> (x, y, s0, s0, vv, unused);
+      store_strip8 (out, g, store, full, vv);
     }
     w0 = w1;
     w1 = w2;
@@ -2241,22 +2159,70 @@ bayer2rgb_colour_kernel (ColourParams cp)
   }
 }
 
-hipError_t launch_colour (const DeepParams &p, const ColourStage &s, bool mhc, bool in8, bool out16, int nframes,
-    hipStream_t stream, long long chunk0, long long nchunks)
+/* ------------------------------------------------------------------------- */
+/* strip launcher                                                              */
+/* ------------------------------------------------------------------------- */
+/* the launch-dependent fields of q (strips of 256 pixels x kStripRows-row chunks, chunks [chunk0, chunk0 + nchunks) of the
+ * batch, nchunks < 0: all) and the grid; *grid = 0: nothing to launch */
+static hipError_t deep_grid (DeepParams &q, int nframes, long long chunk0, long long nchunks, unsigned *grid)
 {
-  if (p.width < 4 || p.height < 3 || (p.width & 1))
+  *grid = 0;
+  q.groups = (q.width + 3) / 4;
+  const int tiles_x = (q.groups + 63) / 64;
+  const long long chunks_per_frame = (q.height + kStripRows - 1) / kStripRows;
+  const long long frames = q.nlist > 0 ? q.nlist : nframes;
+  if (q.nlist > kMaxList || frames <= 0)
+    return frames == 0 ? hipSuccess : hipErrorInvalidValue;
+  const long long total = frames * chunks_per_frame;
+  if (nchunks < 0) {
+    chunk0 = 0;
+    nchunks = total;
+  }
+  if (chunk0 < 0 || chunk0 + nchunks > total)
     return hipErrorInvalidValue;
-  ColourParams q;
+  if (nchunks == 0)
+    return hipSuccess;
+  const long long waves = nchunks * tiles_x;
+  if (total > 0x7fffffffLL || waves > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  q.div_tiles_x = make_fastdiv ((uint32_t) tiles_x);
+  q.div_chunks = make_fastdiv ((uint32_t) chunks_per_frame);
+  q.chunk0 = (uint32_t) chunk0;
+  q.nwaves = (uint32_t) waves;
+  *grid = (unsigned) ((waves + 3) / 4);
+  return hipSuccess;
+}
+
+typedef void (*StripFn) (DeepParams);
+/* [mhc][in8][out16]; bilinear 8 -> 8 is the production (LDS) kernels' */
+static const StripFn kStripKernels[2][2][2] = {
+  { { bayer2rgb_deep_kernel<false, false>, bayer2rgb_deep_kernel<false, true> },
+    { nullptr, bayer2rgb_deep_kernel<true, true> } },
+  { { bayer2rgb_mhc_kernel<false, false>, bayer2rgb_mhc_kernel<false, true> },
+    { bayer2rgb_mhc_kernel<true, false>, bayer2rgb_mhc_kernel<true, true> } },
+};
+
+hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,
+    long long chunk0, long long nchunks)
+{
+  const StripFn fn = kStripKernels[kind.mhc][kind.in8][kind.out16];
+  if (p.width < 4 || p.height < 3 || (p.width & 1) || (!stage && !fn))
+    return hipErrorInvalidValue;
+  ColourParams q;               /* q.d alone is the argument of the plain kernels */
   q.d = p;
   unsigned grid = 0;
-  const hipError_t e = deep_grid (q.d, kMhcRows, nframes, chunk0, nchunks, &grid);
+  const hipError_t e = deep_grid (q.d, nframes, chunk0, nchunks, &grid);
   if (e != hipSuccess || grid == 0)
     return e;
-  q.mhc = mhc;
-  q.in8 = in8;
-  q.out16 = out16;
-  q.s = s;
-  hipLaunchKernelGGL (bayer2rgb_colour_kernel, dim3 (grid), dim3 (256), 0, stream, q);
+  if (stage) {
+    q.mhc = kind.mhc;
+    q.in8 = kind.in8;
+    q.out16 = kind.out16;
+    q.s = *stage;
+    hipLaunchKernelGGL (bayer2rgb_colour_kernel, dim3 (grid), dim3 (256), 0, stream, q);
+  } else {
+    hipLaunchKernelGGL (fn, dim3 (grid), dim3 (256), 0, stream, q.d);
+  }
   return hipGetLastError ();
 }
 
