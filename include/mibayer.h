@@ -196,7 +196,11 @@ typedef struct mibayer_cfg {
  *           in the four layouts of the 8-bit path (ARGB64 = 1,2,3).  Without DST_16BIT the 4-byte formats:
  *           v >> (bits - 8), truncating, alpha 255.  An 8-bit mosaic with 16-bit output is v << 8.
  * Strides: 16-bit samples src_stride default 2*width, >= 2*width, multiple of 4; DST_16BIT dst_stride default
- * 8*width, >= 8*width, multiple of 8.  Geometry as the 8-bit path (even width >= 4, height >= 3).  Any of the four
+ * 8*width, >= 8*width, multiple of 8.  Device-path base pointers (d_src, d_dst, every entry of a list) and the frame
+ * pitches of a batch need only be multiples of 4, whatever the strides, in a deep, MHC or COLOUR context alike -- the
+ * kernels' vector loads and stores ask for dword alignment only -- so a source at 4 mod 8 and an 8-byte-pixel
+ * destination at 4 mod 8 are valid; anything else is MIBAYER_ERR_ARG (MIBAYER_ERR_GEOMETRY for a pitch).
+ * Geometry as the 8-bit path (even width >= 4, height >= 3).  Any of the four
  * together with MIBAYER_FLAG_RGB2BAYER, SRC_BITS outside {0, 10, 12, 14, 16} or an endianness flag without its
  * depth is MIBAYER_ERR_ARG.  Every host / device / list / pool entry point works on a deep context; the host path
  * accepts MIBAYER_FLAG_HIPGRAPH and runs without graphs (as rgb2bayer does).  mibayer_autotune[_list],
