@@ -151,6 +151,28 @@ def colour_tone(curve, gamma=2.2):
     return list(out)
 
 
+class StatsZone(ctypes.Structure):
+    """struct mibayer_stats_zone (include/mibayer.h): per CFA site s = 2 (y & 1) + (x & 1) of one zone"""
+    _fields_ = [("sum", ctypes.c_uint64 * 4), ("count", ctypes.c_uint32 * 4), ("clipped", ctypes.c_uint32 * 4)]
+
+
+# numpy view of an array of StatsZone
+STATS_DTYPE = np.dtype([("sum", np.uint64, 4), ("count", np.uint32, 4), ("clipped", np.uint32, 4)])
+STATS_MAX_ZONES = 64
+
+
+def stats_grey_world(zones, pattern, black=None):
+    """mibayer_stats_grey_world: (ok, (gain_r, 1, gain_b)) from a STATS_DTYPE array of zones (no device needed)"""
+    zones = np.ascontiguousarray(zones, STATS_DTYPE).reshape(-1)
+    gains = (ctypes.c_double * 3)()
+    b = None if black is None else (ctypes.c_double * 3)(*[float(v) for v in black])
+    pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
+    rc = lib().mibayer_stats_grey_world(_ptr(zones), zones.size, pat, b, gains)
+    if rc < 0:
+        raise MibayerError(rc, "mibayer_stats_grey_world")
+    return rc, tuple(gains)
+
+
 class PoolCfg(ctypes.Structure):
     """struct mibayer_pool_cfg (include/mibayer.h)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("stream", Cfg), ("ndevices", ctypes.c_int32),
@@ -265,6 +287,14 @@ ABI = {
     "mibayer_colour_matrix": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(ctypes.c_int32)]),
     "mibayer_colour_tone": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_uint32)]),
+    "mibayer_stats_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_uint32, ctypes.c_uint32, _vp, _vp]),
+    "mibayer_set_stats": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]),
+    "mibayer_frame_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mibayer_pool_set_stats": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32]),
+    "mibayer_pool_frame_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mibayer_stats_grey_world": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                                ctypes.POINTER(ctypes.c_double)]),
 }
 
 
@@ -369,12 +399,25 @@ class Pool:
         self._h = _vp()
         _check(lib().mibayer_pool_create(ctypes.byref(pc), ctypes.byref(self._h)), "mibayer_pool_create")
         self.capacity = lib().mibayer_pool_capacity(self._h)
+        self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
         if isinstance(deep.get("colour"), Colour):
             self.set_colour(deep["colour"])
 
     def set_colour(self, colour):
         """mibayer_pool_set_colour: the colour stage of every shard, for the frames submitted from now on"""
         _check(lib().mibayer_pool_set_colour(self._h, ctypes.byref(colour)), "mibayer_pool_set_colour")
+
+    def set_stats(self, zones_x, zones_y, lo=0, hi=0):
+        """mibayer_pool_set_stats: zone statistics for the frames submitted from now on; (0, 0) = off"""
+        _check(lib().mibayer_pool_set_stats(self._h, zones_x, zones_y, lo, hi), "mibayer_pool_set_stats")
+        if zones_x and zones_y:
+            self._zones = (zones_y, zones_x)
+
+    def frame_stats(self):
+        """mibayer_pool_frame_stats: (zones_y, zones_x) STATS_DTYPE array of the frame wait() handed back last"""
+        out = np.zeros(self._zones, STATS_DTYPE)
+        _check(lib().mibayer_pool_frame_stats(self._h, _ptr(out), out.size), "mibayer_pool_frame_stats")
+        return out
 
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_pool_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_pool_submit")
@@ -472,6 +515,7 @@ class Context:
         self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT))
         self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
         self.colour = bool(out.flags & FLAG_COLOUR)
+        self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
         if isinstance(deep.get("colour"), Colour):
             self.set_colour(deep["colour"])
 
@@ -483,6 +527,47 @@ class Context:
         out = Colour()
         _check(lib().mibayer_get_colour(self._h, ctypes.byref(out)), "mibayer_get_colour")
         return out
+
+    # -- mosaic zone statistics -------------------------------------------------------------
+    def stats_device(self, d_src, d_stats, zones_x, zones_y, lo, hi, nframes=1, src_frame_bytes=None, stream="ctx"):
+        """mibayer_stats_device: d_stats receives nframes * zones_y * zones_x StatsZone (64 bytes each)"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        _check(lib().mibayer_stats_device(self._h, _vp(d_src), src_frame_bytes or self.src_bytes, nframes, zones_x,
+                                          zones_y, lo, hi, _vp(d_stats), _vp(s)), "mibayer_stats_device")
+
+    def set_stats(self, zones_x, zones_y, lo=0, hi=0):
+        """mibayer_set_stats: zone statistics for the host-path frames accepted from now on; (0, 0) = off"""
+        _check(lib().mibayer_set_stats(self._h, zones_x, zones_y, lo, hi), "mibayer_set_stats")
+        if zones_x and zones_y:
+            self._zones = (zones_y, zones_x)
+
+    def frame_stats(self):
+        """mibayer_frame_stats: (zones_y, zones_x) STATS_DTYPE array of the frame handed back last"""
+        out = np.zeros(self._zones, STATS_DTYPE)
+        _check(lib().mibayer_frame_stats(self._h, _ptr(out), out.size), "mibayer_frame_stats")
+        return out
+
+    def stats_batch_via_device(self, frames, zones_x, zones_y, lo, hi, src_frame_bytes=None):
+        """frames: (N, ...) on the host, each src_frame_bytes (default: one frame) long -> (N, zones_y, zones_x)
+        STATS_DTYPE through ONE mibayer_stats_device launch; d_stats is pre-filled with junk"""
+        frames = np.ascontiguousarray(frames)
+        n = frames.shape[0]
+        frames = frames.view(np.uint8).reshape(n, -1)
+        pitch = src_frame_bytes or self.src_bytes
+        assert frames.shape[1] == pitch
+        nz = n * zones_x * zones_y
+        d_src = self.device_alloc(n * pitch)
+        d_stats = self.device_alloc(nz * 64)
+        try:
+            self.to_device(d_src, frames)
+            self.to_device(d_stats, np.full(nz * 64, 0xA5, np.uint8))
+            self.stats_device(d_src, d_stats, zones_x, zones_y, lo, hi, n, pitch)
+            self.sync()
+            out = self.from_device(d_stats, nz * 64)
+        finally:
+            self.device_free(d_src)
+            self.device_free(d_stats)
+        return out.view(STATS_DTYPE).reshape(n, zones_y, zones_x)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):

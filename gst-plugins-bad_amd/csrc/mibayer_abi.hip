@@ -131,6 +131,13 @@ struct Range {
   }
 };
 
+/* a zone grid and its sample range (mibayer_set_stats); zones_x = 0: statistics off */
+struct StatsGrid {
+  int zones_x = 0, zones_y = 0;
+  uint32_t lo = 0, hi = 0;
+};
+constexpr size_t kStatsSlotBytes = (size_t) MIBAYER_STATS_MAX_ZONES * MIBAYER_STATS_MAX_ZONES * sizeof (mibayer_stats_zone);
+
 constexpr int kMaxHostBands = 8;
 constexpr int kInverseBandUnit = 16;    /* rows; a multiple of every rows-per-block of the rgb2bayer kernel */
 
@@ -162,6 +169,11 @@ struct Slot {
   /* MIBAYER_FLAG_COLOUR: the stage of the frame in the slot, taken ONCE when the frame is accepted -- every band of
    * the frame launches with it, whatever mibayer_set_colour does meanwhile */
   ColourStage stage;
+  /* mibayer_set_stats: the grid of the frame in the slot (zones_x = 0: none), taken when the frame is accepted like the
+   * stage; its zones on the device and, downloaded behind the frame, in pinned host memory */
+  StatsGrid grid;
+  mibayer_stats_zone *d_stats = nullptr;
+  mibayer_stats_zone *h_stats = nullptr;
 };
 
 int device_count_cached ()
@@ -305,6 +317,12 @@ struct mibayer_ctx {
   mibayer_colour colour_user;           /* as set (mibayer_get_colour) */
   ColourStage colour_stage;             /* as the kernel takes it */
   DeepParams deep_args;                 /* the launch-independent fields, made at create */
+  /* mibayer_set_stats / mibayer_frame_stats: the grid of the frames accepted from now on, and the zones of the frame
+   * handed back last (last_grid.zones_x = 0: none) */
+  mutable std::mutex stats_mu;
+  StatsGrid stats_grid;
+  StatsGrid last_grid;
+  std::vector<mibayer_stats_zone> last_zones;
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -1557,9 +1575,11 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
 {
   if (how == RELEASE_ORPHAN) {
     Wedge *w = c->wedge;
-    for (void *m : { (void *) s.d_src, (void *) s.d_dst })
+    for (void *m : { (void *) s.d_src, (void *) s.d_dst, (void *) s.d_stats })
       if (m)
         w->dev_mem.push_back (m);
+    if (s.h_stats)
+      mibayer_host_free (s.h_stats);    /* goes on the deferred list while a wedge is outstanding */
     for (hipEvent_t ev : { s.ev_in, s.ev_kernel, s.ev_out })
       if (ev)
         w->events.push_back (ev);
@@ -1589,6 +1609,10 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
     cached_free (c->device, s.d_src, c->src_bytes);
     cached_free (c->device, s.d_dst, c->dst_bytes);
   }
+  if (s.d_stats)
+    (void) hipFree (s.d_stats);
+  if (s.h_stats)
+    mibayer_host_free (s.h_stats);
   if (s.ev_in)
     (void) hipEventDestroy (s.ev_in);
   if (s.ev_kernel)
@@ -1802,6 +1826,189 @@ extern "C" int mibayer_launch_geometry (const mibayer_ctx *c, int nframes,
   return MIBAYER_OK;
 }
 
+/* ---- mosaic zone statistics (group `stats`) -------------------------------------------- */
+
+/* the argument checks of mibayer_stats_device / mibayer_set_stats (include/mibayer.h) and the kernel's arguments */
+static int stats_params (const mibayer_ctx *c, const StatsGrid &g, StatsParams *q)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  const mibayer_cfg &f = c->cfg;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
+  if (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1 || g.zones_y > MIBAYER_STATS_MAX_ZONES
+      || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.lo > g.hi || g.hi > vmax)
+    return MIBAYER_ERR_ARG;
+  memset (q, 0, sizeof *q);
+  q->width = f.width;
+  q->height = f.height;
+  q->src_stride = f.src_stride;
+  q->in8 = bits == 0;
+  q->in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
+  q->mask2 = vmax * 0x00010001u;
+  q->lo = g.lo;
+  q->hi = g.hi;
+  q->zones_x = g.zones_x;
+  q->zones_y = g.zones_y;
+  q->ch = 2 * (((f.height + 1) / 2 + g.zones_y - 1) / g.zones_y);     /* H/2 unrounded: an odd last row has a zone */
+  q->div_cw = make_fastdiv ((uint32_t) (2 * ((f.width / 2 + g.zones_x - 1) / g.zones_x)));
+  return MIBAYER_OK;
+}
+
+/* zeroes `d_stats` and launches the kernel over `nframes` frames on `stream` */
+static int enqueue_stats (StatsParams &q, const void *d_src, size_t src_frame_bytes, int nframes,
+    mibayer_stats_zone *d_stats, hipStream_t stream)
+{
+  q.src = (const uint8_t *) d_src;
+  q.src_frame_bytes = src_frame_bytes;
+  q.stats = (unsigned long long *) d_stats;
+  const size_t bytes = (size_t) nframes * (size_t) q.zones_x * (size_t) q.zones_y * sizeof (mibayer_stats_zone);
+  HIP_TRY (hipMemsetAsync (d_stats, 0, bytes, stream));
+  HIP_TRY (launch_stats (q, nframes, stream));
+  return MIBAYER_OK;
+}
+
+static void mark_dirty (mibayer_ctx *c, hipStream_t s);
+
+extern "C" int mibayer_stats_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes,
+    int zones_x, int zones_y, uint32_t lo, uint32_t hi, mibayer_stats_zone *d_stats, void *hip_stream)
+{
+  if (!c || !d_src || !d_stats || nframes < 0)
+    return MIBAYER_ERR_ARG;
+  StatsGrid g;
+  g.zones_x = zones_x;
+  g.zones_y = zones_y;
+  g.lo = lo;
+  g.hi = hi;
+  StatsParams q;
+  const int rc = stats_params (c, g, &q);
+  if (rc != MIBAYER_OK)
+    return rc;
+  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3)))
+    return MIBAYER_ERR_GEOMETRY;
+  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_stats) & 7))
+    return MIBAYER_ERR_ARG;
+  if (nframes == 0)
+    return MIBAYER_OK;
+  DeviceGuard guard (c->device);
+  if (!guard.ok)
+    return MIBAYER_ERR_HIP;
+  Range r ("mibayer:stats_device");
+  mark_dirty (c, (hipStream_t) hip_stream);
+  return enqueue_stats (q, d_src, src_frame_bytes, nframes, d_stats, (hipStream_t) hip_stream);
+}
+
+extern "C" int mibayer_set_stats (mibayer_ctx *c, int zones_x, int zones_y, uint32_t lo, uint32_t hi)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  StatsGrid g;
+  if (zones_x != 0 || zones_y != 0) {
+    g.zones_x = zones_x;
+    g.zones_y = zones_y;
+    g.lo = lo;
+    g.hi = hi;
+    StatsParams q;
+    const int rc = stats_params (c, g, &q);
+    if (rc != MIBAYER_OK)
+      return rc;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->stats_grid = g;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_frame_stats (mibayer_ctx *c, mibayer_stats_zone *out, int nzones)
+{
+  if (!c || !out)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (c->last_grid.zones_x == 0)
+    return MIBAYER_ERR_EMPTY;
+  if (nzones != (int) c->last_zones.size ())
+    return MIBAYER_ERR_ARG;
+  memcpy (out, c->last_zones.data (), c->last_zones.size () * sizeof (mibayer_stats_zone));
+  return MIBAYER_OK;
+}
+
+/* a frame is accepted into slot `s`: its grid, and the slot's zone buffers when it has one */
+static int slot_take_stats (mibayer_ctx *c, Slot &s)
+{
+  {
+    std::lock_guard<std::mutex> lk (c->stats_mu);
+    s.grid = c->stats_grid;
+  }
+  if (s.grid.zones_x == 0)
+    return MIBAYER_OK;
+  if (!s.d_stats)
+    HIP_TRY (hipMalloc ((void **) &s.d_stats, kStatsSlotBytes));
+  if (!s.h_stats)
+    HIP_TRY (hipHostMalloc ((void **) &s.h_stats, kStatsSlotBytes, hipHostMallocDefault));
+  return MIBAYER_OK;
+}
+
+/* the statistics launch of the frame in slot `s` on the compute queue, behind the upload of its last row */
+static int slot_launch_stats (mibayer_ctx *c, Slot &s)
+{
+  if (s.grid.zones_x == 0)
+    return MIBAYER_OK;
+  StatsParams q;
+  const int rc = stats_params (c, s.grid, &q);
+  if (rc != MIBAYER_OK)
+    return rc;
+  Range r ("mibayer:stats");
+  return enqueue_stats (q, s.d_src, c->src_bytes, 1, s.d_stats, c->s_compute);
+}
+
+/* ... and their download on the download queue, behind the event of that launch */
+static int slot_download_stats (mibayer_ctx *c, Slot &s)
+{
+  if (s.grid.zones_x == 0)
+    return MIBAYER_OK;
+  HIP_TRY (hipMemcpyAsync (s.h_stats, s.d_stats,
+          (size_t) s.grid.zones_x * s.grid.zones_y * sizeof (mibayer_stats_zone), hipMemcpyDeviceToHost, c->s_d2h));
+  return MIBAYER_OK;
+}
+
+/* the frame of slot `s` has been handed back: mibayer_frame_stats answers for it from now on */
+static void slot_retire_stats (mibayer_ctx *c, const Slot &s)
+{
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->last_grid = s.grid;
+  if (s.grid.zones_x == 0)
+    c->last_zones.clear ();
+  else
+    c->last_zones.assign (s.h_stats, s.h_stats + (size_t) s.grid.zones_x * s.grid.zones_y);
+}
+
+extern "C" int mibayer_stats_grey_world (const mibayer_stats_zone *zones, int nzones, int pattern,
+    const double black[3], double gains[3])
+{
+  if (!zones || !gains || nzones < 1 || pattern < MIBAYER_BGGR || pattern > MIBAYER_RGGB)
+    return MIBAYER_ERR_ARG;
+  /* colour (0 = R, 1 = G, 2 = B) of site s = 2 (y & 1) + (x & 1), per Bayer order */
+  static const int kSiteColour[4][4] = { { 2, 1, 1, 0 }, { 1, 2, 0, 1 }, { 1, 0, 2, 1 }, { 0, 1, 1, 2 } };
+  unsigned long long sum[3] = { 0, 0, 0 }, n[3] = { 0, 0, 0 };
+  for (int z = 0; z < nzones; z++)
+    for (int site = 0; site < 4; site++) {
+      sum[kSiteColour[pattern][site]] += zones[z].sum[site];
+      n[kSiteColour[pattern][site]] += zones[z].count[site];
+    }
+  gains[0] = gains[1] = gains[2] = 1.0;
+  double m[3];
+  for (int k = 0; k < 3; k++) {
+    if (n[k] == 0)
+      return 0;
+    m[k] = (double) sum[k] / (double) n[k] - (black ? black[k] : 0.0);
+    if (!(m[k] > 0.0))
+      return 0;
+  }
+  const double r = m[1] / m[0], b = m[1] / m[2];
+  gains[0] = r < 1.0 / 16 ? 1.0 / 16 : r > 15.99 ? 15.99 : r;
+  gains[2] = b < 1.0 / 16 ? 1.0 / 16 : b > 15.99 ? 15.99 : b;
+  return 1;
+}
+
 /* ---- host-memory frame path -------------------------------------------------------- */
 
 /* device-side frames and events of one slot; `bands`: per-band events too */
@@ -1996,6 +2203,11 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
         c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
+    if (b == nb - 1) {          /* every row is on the device: the statistics once over the whole mosaic */
+      rc = slot_launch_stats (c, s);
+      if (rc != MIBAYER_OK)
+        return rc;
+    }
     HIP_TRY (hipEventRecord (s.ev_band_kernel[b], c->s_compute));
     HIP_TRY (hipStreamWaitEvent (c->s_d2h, s.ev_band_kernel[b], 0));
     const size_t doff = (size_t) y0 * f.dst_stride;
@@ -2010,6 +2222,9 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
               (size_t) (y1 - y0), hipMemcpyDeviceToHost, c->s_d2h));
     }
   }
+  const int src_rc = slot_download_stats (c, s);
+  if (src_rc != MIBAYER_OK)
+    return src_rc;
   HIP_TRY (hipEventRecord (s.ev_out, c->s_d2h));
   return MIBAYER_OK;
 }
@@ -2107,6 +2322,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
         c->s_compute, 0, -1, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
+    const int stats_rc = slot_launch_stats (c, s);
+    if (stats_rc != MIBAYER_OK)
+      return stats_rc;
     HIP_TRY (hipEventRecord (s.ev_kernel, c->s_compute));
   }
   Range r ("mibayer:d2h");
@@ -2121,6 +2339,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
             (size_t) c->cfg.dst_stride, row_bytes, (size_t) c->cfg.height,
             hipMemcpyDeviceToHost, c->s_d2h));
   }
+  const int stats_rc = slot_download_stats (c, s);
+  if (stats_rc != MIBAYER_OK)
+    return stats_rc;
   HIP_TRY (hipEventRecord (s.ev_out, c->s_d2h));
   return MIBAYER_OK;
 }
@@ -2142,8 +2363,12 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   Slot &s = c->ring[(size_t) c->head];
   if (c->colour)
     colour_snapshot (c, &s.stage);      /* one stage per frame, however many bands it is launched in */
+  rc = slot_take_stats (c, s);
+  if (rc != MIBAYER_OK)
+    return rc;
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
-  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep;
+  /* (the captured graphs hold the demosaic launch only: a frame with statistics is launched without them) */
+  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0;
   if (want_graph && c->graph_mode == 1
       && (size_t) c->cfg.dst_stride == row_bytes) {
     rc = graph_submit (c, s, src, dst);
@@ -2210,6 +2435,7 @@ static int wait_locked (mibayer_ctx *c, void **tag)
   }
   if (tag)
     *tag = s.tag;
+  slot_retire_stats (c, s);
   c->tail = (c->tail + 1) % (int) c->ring.size ();
   c->pending--;
   return MIBAYER_OK;
@@ -2287,14 +2513,20 @@ extern "C" int mibayer_internal_run_spare (mibayer_ctx *c, const uint8_t *src,
     return MIBAYER_ERR_TIMEOUT;
   if (c->colour)
     colour_snapshot (c, &c->spare.stage);
-  int rc = enqueue_plain (c, c->spare, src, dst, written_row_bytes (c));
+  int rc = slot_take_stats (c, c->spare);
+  if (rc == MIBAYER_OK)
+    rc = enqueue_plain (c, c->spare, src, dst, written_row_bytes (c));
   if (rc != MIBAYER_OK) {
     /* nothing of a half-queued frame may touch the buffers after the error */
     fence_queues (c);
     return rc;
   }
   Range r ("mibayer:wait");
-  return wait_event (c, c->spare.ev_out, true);
+  rc = wait_event (c, c->spare.ev_out, true);
+  if (rc == MIBAYER_OK)
+    slot_retire_stats (c, c->spare);    /* mibayer_frame_stats answers for this frame: the caller owns the context's
+                                           retiring side while it re-does frames (mibayer_pool.cpp) */
+  return rc;
 }
 
 extern "C" int mibayer_internal_is_pageable (const void *p)

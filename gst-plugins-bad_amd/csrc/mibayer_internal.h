@@ -295,6 +295,30 @@ struct StripKind { bool mhc, in8, out16; };
 hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1);
 
+/* Mosaic zone statistics (mosaic_stats_kernel; include/mibayer.h, group `stats`): read-only over the mosaic, one kernel
+ * for both sample widths and byte orders (uniform run-time branches) */
+constexpr int kStatsSegRows = 64;       /* rows a workgroup walks; even, so a segment starts on an even row */
+constexpr int kStatsMaxZones = 64;
+struct StatsParams {
+  const uint8_t *src;
+  unsigned long long src_frame_bytes;
+  unsigned long long *stats;    /* nframes x zones_y x zones_x zones of 64 bytes: sum[4] (64-bit), count[4], clipped[4] */
+  int width, height, src_stride;
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a source dword: identity or a byte swap per 16-bit word */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  uint32_t lo, hi;
+  int zones_x, zones_y;
+  int ch;                       /* rows of a zone */
+  FastDiv div_cw;               /* pixels of a zone */
+  /* filled by launch_stats */
+  int row_dwords;               /* dwords of a row that hold columns < width (the last one may hold two columns past it) */
+  int segs;                     /* segments of kStatsSegRows rows per zone row */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row */
+};
+/* one launch over `nframes` frames; p.stats must have been zeroed on the stream before */
+hipError_t launch_stats (const StatsParams &p, int nframes, hipStream_t stream);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

@@ -2227,6 +2227,141 @@ hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage 
 }
 
 /* ------------------------------------------------------------------------- */
+/* mosaic zone statistics                                                      */
+/* ------------------------------------------------------------------------- */
+/* Per zone and CFA site: sum and count of the samples in [lo, hi] and the number above hi (include/mibayer.h, group
+ * `stats`).  Read-only over the mosaic.  A workgroup is four waves side by side, each on a strip of 64 dwords, walking the
+ * (at most kStatsSegRows) rows of one segment of ONE zone row, kStatsAhead dword loads in flight per lane.  A lane's dword
+ * holds four 8-bit or two 16-bit samples: two column pairs ("halves") at most, and since a zone is an even number of
+ * pixels wide a pair never straddles two zones -- a lane keeps sum / count / clipped per half, column parity and row
+ * parity in 32-bit registers (a segment adds at most kStatsSegRows / 2 samples of 16 bits to one of them: no overflow),
+ * and adds them once, at the end, into the workgroup's LDS table [zone column][site] with LDS atomics, 64-bit for the
+ * sums.  After a barrier the workgroup issues one global atomic per non-zero table entry.  Integer additions: the
+ * result does not depend on their order. */
+constexpr int kStatsAhead = 8;
+
+__global__ void __launch_bounds__ (256)
+mosaic_stats_kernel (StatsParams p)
+{
+  __shared__ unsigned long long t_sum[kStatsMaxZones * 4];
+  __shared__ uint32_t t_cnt[kStatsMaxZones * 4];
+  __shared__ uint32_t t_clip[kStatsMaxZones * 4];
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int zy = (int) blockIdx.y / p.segs;
+  const int seg = (int) blockIdx.y - zy * p.segs;
+  const int y0 = zy * p.ch + seg * kStatsSegRows;
+  int y1 = y0 + kStatsSegRows;
+  y1 = y1 < (zy + 1) * p.ch ? y1 : (zy + 1) * p.ch;
+  y1 = y1 < p.height ? y1 : p.height;
+  if (y0 >= y1)                 /* the whole workgroup: an empty trailing zone row, or a short last segment */
+    return;
+  t_sum[threadIdx.x] = 0;
+  t_cnt[threadIdx.x] = 0;
+  t_clip[threadIdx.x] = 0;
+  __syncthreads ();
+
+  const int g = (int) (strip * 256u + threadIdx.x);     /* dword of the row */
+  if (g < p.row_dwords) {
+    const int x0 = p.in8 ? 4 * g : 2 * g;               /* its first column: even, < width */
+    const uint32_t w23 = p.in8 && x0 + 2 < p.width ? 1u : 0u;   /* columns x0+2, x0+3 exist */
+    const uint8_t *col = p.src + frame * p.src_frame_bytes + 4 * (size_t) g;
+    /* [row parity][half][column parity] */
+    uint32_t sum[2][2][2] = {}, cnt[2][2][2] = {}, clip[2][2][2] = {};
+    /* the samples of dword d, in a row of parity rp; w = 0: the row is past the segment (d = 0) */
+    auto add = [&] (uint32_t d, int rp, uint32_t w) {
+      uint32_t v[4];
+      if (p.in8) {
+        v[0] = d & 0xffu;
+        v[1] = (d >> 8) & 0xffu;
+        v[2] = (d >> 16) & 0xffu;
+        v[3] = d >> 24;
+      } else {
+        const uint32_t m = __builtin_amdgcn_perm (d, d, p.in_sel) & p.mask2;
+        v[0] = m & 0xffffu;
+        v[1] = m >> 16;
+        v[2] = v[3] = 0;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t wk = k < 2 ? w : w & w23;
+        const bool in = v[k] - p.lo <= p.hi - p.lo;     /* lo <= v <= hi (lo <= hi) */
+        sum[rp][k >> 1][k & 1] += in ? v[k] * wk : 0u;
+        cnt[rp][k >> 1][k & 1] += in ? wk : 0u;
+        clip[rp][k >> 1][k & 1] += v[k] > p.hi ? wk : 0u;
+      }
+    };
+    int y = y0;                 /* even, and so is kStatsAhead: the row parity below is that of i */
+    for (; y + kStatsAhead <= y1; y += kStatsAhead) {
+      uint32_t d[kStatsAhead];
+#pragma unroll
+      for (int i = 0; i < kStatsAhead; i++)
+        d[i] = __builtin_nontemporal_load ((const uint32_t *) (col + (size_t) (y + i) * (size_t) p.src_stride));
+#pragma unroll
+      for (int i = 0; i < kStatsAhead; i++)
+        add (d[i], i & 1, 1u);
+    }
+    for (; y < y1; y += 2) {    /* the last rows of the segment, a pair at a time */
+      const bool two = y + 1 < y1;
+      const uint32_t d0 = __builtin_nontemporal_load ((const uint32_t *) (col + (size_t) y * (size_t) p.src_stride));
+      const uint32_t d1 = two
+          ? __builtin_nontemporal_load ((const uint32_t *) (col + (size_t) (y + 1) * (size_t) p.src_stride)) : 0u;
+      add (d0, 0, 1u);
+      add (d1, 1, two ? 1u : 0u);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      if (h == 1 && !w23)
+        continue;
+      const uint32_t zx = fastdiv ((uint32_t) (x0 + 2 * h), p.div_cw);
+#pragma unroll
+      for (int site = 0; site < 4; site++) {
+        const uint32_t e = zx * 4u + (uint32_t) site;
+        const uint32_t n = cnt[site >> 1][h][site & 1], c = clip[site >> 1][h][site & 1];
+        if (n) {
+          atomicAdd (&t_sum[e], (unsigned long long) sum[site >> 1][h][site & 1]);
+          atomicAdd (&t_cnt[e], n);
+        }
+        if (c)
+          atomicAdd (&t_clip[e], c);
+      }
+    }
+  }
+  __syncthreads ();
+  /* thread t owns table entry t = zone column t / 4, site t % 4 (columns >= zones_x were never added to) */
+  const uint32_t e = threadIdx.x;
+  unsigned long long *zone = p.stats
+      + 8ull * (((unsigned long long) frame * (uint32_t) p.zones_y + (uint32_t) zy) * (uint32_t) p.zones_x + (e >> 2));
+  if (t_cnt[e]) {
+    atomicAdd (zone + (e & 3u), t_sum[e]);
+    atomicAdd ((uint32_t *) (zone + 4) + (e & 3u), t_cnt[e]);
+  }
+  if (t_clip[e])
+    atomicAdd ((uint32_t *) (zone + 6) + (e & 3u), t_clip[e]);
+}
+
+hipError_t launch_stats (const StatsParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.width < 2 || (p.width & 1) || p.height < 1 || p.zones_x < 1 || p.zones_x > kStatsMaxZones || p.zones_y < 1
+      || p.ch < 2 || (p.ch & 1) || p.div_cw.d < 2 || (p.div_cw.d & 1)
+      || (unsigned long long) p.div_cw.d * (unsigned) p.zones_x < (unsigned) p.width
+      || (long long) p.ch * p.zones_y < p.height)
+    return hipErrorInvalidValue;        /* (a zone column past the LDS table, a pair across two zones) */
+  StatsParams q = p;
+  q.row_dwords = p.in8 ? (p.width + 3) / 4 : p.width / 2;
+  q.segs = (p.ch + kStatsSegRows - 1) / kStatsSegRows;
+  const long long strips = (q.row_dwords + 255) / 256;
+  const long long gy = (long long) q.segs * p.zones_y;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535)
+    return hipErrorInvalidValue;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  hipLaunchKernelGGL (mosaic_stats_kernel, dim3 ((unsigned) (strips * nframes), (unsigned) gy), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

@@ -56,6 +56,9 @@
  * layer that do not have them (tests/check), where a colour request is refused */
 #pragma weak mibayer_set_colour
 #pragma weak mibayer_get_colour
+/* ... and so are the statistics': a pool over such a double refuses mibayer_pool_set_stats */
+#pragma weak mibayer_set_stats
+#pragma weak mibayer_frame_stats
 
 #include <sched.h>
 
@@ -73,6 +76,11 @@
 #include <vector>
 
 namespace {
+
+struct StatsGrid {
+  int zones_x, zones_y;
+  uint32_t lo, hi;
+};
 
 enum FrameState {
   F_DIRECT,     /* in the ring of its shard's context, submitted by the streaming thread */
@@ -98,6 +106,10 @@ struct Frame {
   /* MIBAYER_FLAG_COLOUR pools: the stage the pool held when mibayer_pool_submit accepted the frame; whoever hands the
    * frame to a context -- the caller's thread, a helper thread later, a redo on another shard -- applies it first */
   std::shared_ptr<const mibayer_colour> colour;
+  /* mibayer_pool_set_stats: the grid the pool held when the frame was accepted (NULL: none), applied like the stage;
+   * and the frame's zones, fetched from the context by the thread that retired the frame there */
+  std::shared_ptr<const StatsGrid> grid;
+  std::vector<mibayer_stats_zone> zones;
 };
 
 struct Shard {
@@ -111,6 +123,7 @@ struct Shard {
   int stall_ms = 0;
   std::shared_ptr<const mibayer_colour> applied;        /* the stage its context holds (touched by whichever ONE
                                                            thread hands frames to the context) */
+  std::shared_ptr<const StatsGrid> applied_grid;        /* ... and the statistics grid (NULL: off, as created) */
   std::atomic<long long> completions { 0 };
   std::atomic<long long> fail_after { -1 };     /* fault injection; -1 = never */
   /* helper thread */
@@ -146,6 +159,28 @@ void apply_colour (Shard *sh, const Frame *f)
     return;
   if (mibayer_set_colour (sh->ctx, f->colour.get ()) == MIBAYER_OK)
     sh->applied = f->colour;
+}
+
+/* the same for the frame's statistics grid */
+void apply_stats (Shard *sh, const Frame *f)
+{
+  if (f->grid == sh->applied_grid || !mibayer_set_stats)
+    return;
+  const StatsGrid off = { 0, 0, 0, 0 };
+  const StatsGrid *g = f->grid ? f->grid.get () : &off;
+  if (mibayer_set_stats (sh->ctx, g->zones_x, g->zones_y, g->lo, g->hi) == MIBAYER_OK)
+    sh->applied_grid = f->grid;
+}
+
+/* the context of `sh` has just handed the frame back to this thread: keep its zones with the frame */
+void fetch_stats (Shard *sh, Frame *f)
+{
+  f->zones.clear ();
+  if (!f->grid || !mibayer_frame_stats)
+    return;
+  f->zones.resize ((size_t) f->grid->zones_x * (size_t) f->grid->zones_y);
+  if (mibayer_frame_stats (sh->ctx, f->zones.data (), (int) f->zones.size ()) != MIBAYER_OK)
+    f->zones.clear ();
 }
 
 bool device_failure (int rc)
@@ -249,6 +284,7 @@ void helper_main (Shard *sh)
       sh->ring.push_back (f);
       lk.unlock ();
       apply_colour (sh, f);
+      apply_stats (sh, f);
       const int rc = mibayer_submit (sh->ctx, f->src, f->dst, f);
       lk.lock ();
       if (rc != MIBAYER_OK) {
@@ -272,10 +308,17 @@ void helper_main (Shard *sh)
       int rc = mibayer_wait (sh->ctx, NULL);
       if (rc == MIBAYER_OK && sh->fault_due ())
         rc = MIBAYER_ERR_HIP;
+      std::vector<mibayer_stats_zone> zones;
+      if (rc == MIBAYER_OK && f->grid && mibayer_frame_stats) {
+        zones.resize ((size_t) f->grid->zones_x * (size_t) f->grid->zones_y);
+        if (mibayer_frame_stats (sh->ctx, zones.data (), (int) zones.size ()) != MIBAYER_OK)
+          zones.clear ();
+      }
       lk.lock ();
       if (sh->ring.empty () || sh->ring.front () != f)
         continue;               /* the shard was given up meanwhile */
       if (rc == MIBAYER_OK) {
+        f->zones.swap (zones);
         sh->ring.pop_front ();
         f->state = F_DONE;
         sh->cv_done.notify_all ();
@@ -313,6 +356,11 @@ struct mibayer_pool {
   /* MIBAYER_FLAG_COLOUR: the stage of the frames submitted from now on (NULL: not a colour pool); only the
    * caller's thread touches it, the frames carry their own reference */
   std::shared_ptr<const mibayer_colour> colour;
+  /* mibayer_pool_set_stats: the grid of the frames submitted from now on (NULL: off), and the zones of the frame
+   * mibayer_pool_wait handed back last (has_zones: it had any) */
+  std::shared_ptr<const StatsGrid> grid;
+  std::vector<mibayer_stats_zone> last_zones;
+  bool has_zones = false;
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -650,6 +698,57 @@ extern "C" int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour
   return MIBAYER_OK;
 }
 
+/* The statistics grid of the frames submitted from now on, kept with each frame like the colour stage (apply_stats);
+ * the range checks are the context layer's: the grid is tried on the first shard's context -- whose own frames carry
+ * theirs, and get it back before they are handed over -- so a bad one is refused here and not frames later. */
+extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zones_y, uint32_t lo, uint32_t hi)
+{
+  if (!pool || !mibayer_set_stats || !mibayer_frame_stats)
+    return MIBAYER_ERR_ARG;
+  if (zones_x == 0 && zones_y == 0) {
+    pool->grid.reset ();
+    return MIBAYER_OK;
+  }
+  Shard *probe = NULL;
+  for (Shard *sh : pool->shards)
+    if (sh->alive && !sh->helper_mode) {
+      probe = sh;
+      break;
+    }
+  const StatsGrid g = { zones_x, zones_y, lo, hi };
+  if (probe) {
+    const int rc = mibayer_set_stats (probe->ctx, zones_x, zones_y, lo, hi);
+    if (rc != MIBAYER_OK)
+      return rc;
+    probe->applied_grid = std::make_shared<const StatsGrid> (g);
+    pool->grid = probe->applied_grid;
+    return MIBAYER_OK;
+  }
+  /* every context is driven by a helper thread: the same rule on the resolved configuration */
+  mibayer_cfg f;
+  if (mibayer_get_cfg (pool->shards[0]->ctx, &f) != MIBAYER_OK || (f.flags & MIBAYER_FLAG_RGB2BAYER))
+    return MIBAYER_ERR_ARG;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
+  if (zones_x < 1 || zones_x > MIBAYER_STATS_MAX_ZONES || zones_y < 1 || zones_y > MIBAYER_STATS_MAX_ZONES
+      || zones_x > f.width / 2 || zones_y > f.height / 2 || lo > hi || hi > vmax)
+    return MIBAYER_ERR_ARG;
+  pool->grid = std::make_shared<const StatsGrid> (g);
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_pool_frame_stats (mibayer_pool *pool, mibayer_stats_zone *out, int nzones)
+{
+  if (!pool || !out)
+    return MIBAYER_ERR_ARG;
+  if (!pool->has_zones)
+    return MIBAYER_ERR_EMPTY;
+  if (nzones != (int) pool->last_zones.size ())
+    return MIBAYER_ERR_ARG;
+  memcpy (out, pool->last_zones.data (), pool->last_zones.size () * sizeof (mibayer_stats_zone));
+  return MIBAYER_OK;
+}
+
 extern "C" int mibayer_pool_inject_stall (mibayer_pool *pool, int shard, int ms)
 {
   if (!pool || shard < 0 || shard >= (int) pool->shards.size ())
@@ -737,7 +836,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       sh->stall_ms = 0;
       (void) mibayer_internal_stall (sh->ctx, ms);
     }
-    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour };
+    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {} };
     if (pool->use_helpers && (mibayer_internal_is_pageable (src) || mibayer_internal_is_pageable (dst))
         && !sh->pageable_seen) {
       sh->pageable_seen = true;
@@ -748,6 +847,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       queue_to_helper (sh, &pool->fifo.back ());
     } else {
       apply_colour (sh, &f);
+      apply_stats (sh, &f);
       const int rc = mibayer_submit (sh->ctx, src, dst, tag);
       if (device_failure (rc)) {
         kill_shard (pool, (int) idx, rc, mibayer_last_hip_error ());
@@ -790,8 +890,10 @@ extern "C" int mibayer_pool_wait (mibayer_pool *pool, void **tag)
       int rc = mibayer_wait (sh->ctx, NULL);
       if (rc == MIBAYER_OK && sh->fault_due ())
         rc = MIBAYER_ERR_HIP;
-      if (rc == MIBAYER_OK)
+      if (rc == MIBAYER_OK) {
+        fetch_stats (sh, &f);
         break;
+      }
       if (!device_failure (rc))
         return rc;
       kill_shard (pool, f.shard, rc, mibayer_last_hip_error ());    /* f becomes F_REDO */
@@ -814,6 +916,8 @@ extern "C" int mibayer_pool_wait (mibayer_pool *pool, void **tag)
       /* in flight on a device that ran into the deadline: handed back as lost, in order; its buffers stay the
        * device's until mibayer_pool_reclaim() says otherwise */
       pool->lost.push_back (mibayer_pool::Lost { f.tag, f.shard });
+      pool->has_zones = false;
+      pool->last_zones.clear ();
       if (tag)
         *tag = f.tag;
       pool->shards[(size_t) f.owner]->inflight--;
@@ -854,17 +958,22 @@ extern "C" int mibayer_pool_wait (mibayer_pool *pool, void **tag)
     f.submitted = true;         /* while the spare slot of `to` works on it */
     f.state = F_REDO;
     apply_colour (to, &f);
+    apply_stats (to, &f);
     int rc = mibayer_internal_run_spare (to->ctx, f.src, f.dst);
     if (rc == MIBAYER_OK && to->fault_due ())
       rc = MIBAYER_ERR_HIP;
-    if (rc == MIBAYER_OK)
+    if (rc == MIBAYER_OK) {
+      fetch_stats (to, &f);
       break;
+    }
     if (!device_failure (rc))
       return rc;
     kill_shard (pool, (int) idx, rc, mibayer_last_hip_error ());       /* F_REDO again, or F_LOST after a deadline */
   }
   if (tag)
     *tag = f.tag;
+  pool->has_zones = f.grid && !f.zones.empty ();
+  pool->last_zones.swap (f.zones);
   pool->shards[(size_t) f.owner]->inflight--;
   pool->fifo.pop_front ();
   return MIBAYER_OK;

@@ -281,6 +281,15 @@ element_collect_locked (GstMiBayerElement * self, GstBuffer ** outbuf,
     *gpu_rc = rc;
     return GST_FLOW_ERROR;
   }
+  if (self->awb_on) {
+    /* white-balance=grey-world: the frame's means move the gains of the frames accepted from now on */
+    mibayer_stats_zone zone;
+    mibayer_colour colour;
+
+    if (mibayer_pool_frame_stats (self->pool, &zone, 1) == MIBAYER_OK
+        && gst_mi_awb_step (self->act.colour, (GstMiAwb *) self->awb_gain, &zone, self->format, &colour))
+      (void) mibayer_pool_set_colour (self->pool, &colour);
+  }
   *outbuf = p->outbuf;
   *owned = p->owns_outbuf;
   pending_release (p, TRUE);
@@ -460,6 +469,7 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
   }
   self->pool_stride = 0;
   self->capacity = 0;
+  self->awb_on = FALSE;
 
   /* the colour stage: only when a colour property is off its default (the default output is the reference's bytes) */
   want_colour = !inverse && !gst_mi_colour_props_are_default (self->act.colour);
@@ -534,6 +544,22 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
         g_strdup_printf ("%s: cannot set up the colour stage", LABEL (self)),
         g_strdup_printf ("mibayer_pool_set_colour: %s", mibayer_strerror (rc)));
     return FALSE;
+  }
+  if (want_colour && ((GstMiColourProps *) self->act.colour)->white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD) {
+    guint32 lo, hi;
+
+    gst_mi_awb_start (self->act.colour, (GstMiAwb *) self->awb_gain, self->src_bits ? self->src_bits : 8, &lo, &hi);
+    rc = mibayer_pool_set_stats && mibayer_pool_frame_stats && mibayer_stats_grey_world
+        ? mibayer_pool_set_stats (self->pool, 1, 1, lo, hi) : MIBAYER_ERR_ARG;
+    if (rc != MIBAYER_OK) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up white-balance=grey-world", LABEL (self)),
+          g_strdup_printf ("mibayer_pool_set_stats (1, 1, %u, %u): %s", lo, hi, mibayer_strerror (rc)));
+      return FALSE;
+    }
+    self->awb_on = TRUE;
   }
   /* a GPU that stops answering is dropped like one that reports an error, after this long */
   (void) mibayer_pool_set_wait_timeout (self->pool, self->act.timeout_ms);

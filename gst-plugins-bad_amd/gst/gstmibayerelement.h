@@ -81,6 +81,8 @@ struct _GstMiBayerElement
   mibayer_pool *pool;
   gint pool_stride;
   gint capacity;                /* frames the pool may hold in flight (shrinks when a device is dropped) */
+  gboolean awb_on;              /* white-balance=grey-world: the pool measures every frame (1 x 1 statistics) ... */
+  gdouble awb_gain[2];          /* ... and these are the red and blue gain in use (GstMiAwb, gstmicolour.h) */
   GQueue pending;               /* PendingFrame*, oldest first */
   GQueue ready;                 /* GstBuffer*: finished outputs collected early (the pool shrank), oldest first */
   GQueue quarantine;            /* PendingFrame*: frames lost on a GPU that ran into the wait deadline; both buffers

@@ -1,10 +1,14 @@
 /*
  * gstmicolour.h -- the colour-stage properties of bayer2rgb and hipbayer2rgb (MIBAYER_FLAG_COLOUR, include/mibayer.h):
- * black-level, red-/green-/blue-gain, ccm, tone-curve, gamma.  One definition for both plugins; each includes this
- * header once, after defining GST_MI_COLOUR_TONE_TYPE_NAME (the two plugins may be loaded into one process, so the
- * enum type needs a name per plugin).
+ * black-level, red-/green-/blue-gain, ccm, tone-curve, gamma, and the automatic white balance on top of it:
+ * white-balance (manual / grey-world) and awb-speed.  One definition for both plugins; each includes this header once,
+ * after defining GST_MI_COLOUR_TONE_TYPE_NAME (the two plugins may be loaded into one process, so the enum types need
+ * a name per plugin; the white-balance enum's is that name with "WhiteBalance" appended).
  *
  * With every property at its default an element does not set the flag: its output stays the reference's bytes.
+ * white-balance=grey-world sets the flag on its own: the element measures every frame it gets back (1 x 1 mosaic zone
+ * statistics, group `stats` of include/mibayer.h) and moves its red and blue gain towards the grey-world gains of that
+ * frame (gst_mi_awb_step), for the frames it accepts afterwards.
  *
  * The colour entry points of libmibayer are bound WEAKLY: the plugins also load against builds of the library
  * interface that do not have them (the test doubles of tests/check), where a non-default colour request ends in an
@@ -24,6 +28,18 @@
 #pragma weak mibayer_colour_tone
 #pragma weak mibayer_set_colour
 #pragma weak mibayer_pool_set_colour
+#pragma weak mibayer_stats_device
+#pragma weak mibayer_set_stats
+#pragma weak mibayer_frame_stats
+#pragma weak mibayer_pool_set_stats
+#pragma weak mibayer_pool_frame_stats
+#pragma weak mibayer_stats_grey_world
+
+enum
+{
+  GST_MI_WHITE_BALANCE_MANUAL = 0,
+  GST_MI_WHITE_BALANCE_GREY_WORLD
+};
 
 typedef struct
 {
@@ -32,7 +48,15 @@ typedef struct
   gchar *ccm;                   /* nine comma-separated numbers, row-major; NULL / "" = identity */
   gint tone_curve;              /* MIBAYER_TONE_* */
   gdouble gamma;
+  gint white_balance;           /* GST_MI_WHITE_BALANCE_* */
+  gdouble awb_speed;
 } GstMiColourProps;
+
+/* the running state of white-balance=grey-world: the red and blue gain in use (gst_mi_awb_start / gst_mi_awb_step) */
+typedef struct
+{
+  gdouble gain[2];
+} GstMiAwb;
 
 /* the ids an element's property enum reserves, in this order, from its `first` id on */
 enum
@@ -44,10 +68,30 @@ enum
   GST_MI_COLOUR_PROP_CCM,
   GST_MI_COLOUR_PROP_TONE_CURVE,
   GST_MI_COLOUR_PROP_GAMMA,
+  GST_MI_COLOUR_PROP_WHITE_BALANCE,
+  GST_MI_COLOUR_PROP_AWB_SPEED,
   GST_MI_COLOUR_N_PROPS
 };
 
 #define GST_MI_COLOUR_DEFAULT_GAMMA 2.2
+#define GST_MI_COLOUR_DEFAULT_AWB_SPEED 0.25
+
+static GType
+gst_mi_colour_white_balance_get_type (void)
+{
+  static gsize type = 0;
+  static const GEnumValue values[] = {
+    {GST_MI_WHITE_BALANCE_MANUAL, "Manual: the red-/green-/blue-gain properties", "manual"},
+    {GST_MI_WHITE_BALANCE_GREY_WORLD,
+        "Grey world: red and blue gain follow the channel means of the frames", "grey-world"},
+    {0, NULL, NULL}
+  };
+  if (g_once_init_enter (&type)) {
+    GType t = g_enum_register_static (GST_MI_COLOUR_TONE_TYPE_NAME "WhiteBalance", values);
+    g_once_init_leave (&type, t);
+  }
+  return (GType) type;
+}
 
 static GType
 gst_mi_colour_tone_get_type (void)
@@ -74,6 +118,8 @@ gst_mi_colour_props_init (GstMiColourProps * p)
   p->ccm = NULL;
   p->tone_curve = MIBAYER_TONE_LINEAR;
   p->gamma = GST_MI_COLOUR_DEFAULT_GAMMA;
+  p->white_balance = GST_MI_WHITE_BALANCE_MANUAL;
+  p->awb_speed = GST_MI_COLOUR_DEFAULT_AWB_SPEED;
 }
 
 static void
@@ -93,12 +139,13 @@ gst_mi_colour_props_copy (GstMiColourProps * dst, const GstMiColourProps * src)
   dst->ccm = ccm;
 }
 
-/* gamma alone changes nothing: it is read by tone-curve=gamma only */
+/* gamma alone changes nothing: it is read by tone-curve=gamma only (and awb-speed by white-balance=grey-world) */
 static gboolean
 gst_mi_colour_props_are_default (const GstMiColourProps * p)
 {
   return p->black_level == 0 && p->gain[0] == 1.0 && p->gain[1] == 1.0 && p->gain[2] == 1.0
-      && (p->ccm == NULL || p->ccm[0] == '\0') && p->tone_curve == MIBAYER_TONE_LINEAR;
+      && (p->ccm == NULL || p->ccm[0] == '\0') && p->tone_curve == MIBAYER_TONE_LINEAR
+      && p->white_balance == GST_MI_WHITE_BALANCE_MANUAL;
 }
 
 /* The mibayer_colour of the properties, built with the library's helpers so that everybody rounds alike.  FALSE with a
@@ -152,6 +199,46 @@ gst_mi_colour_props_build (const GstMiColourProps * p, mibayer_colour * out, gch
   return TRUE;
 }
 
+/* white-balance=grey-world: the sample range of the 1 x 1 statistics at `depth` bits, and the gains to start from */
+static G_GNUC_UNUSED void
+gst_mi_awb_start (const GstMiColourProps * p, GstMiAwb * awb, gint depth, guint32 * lo, guint32 * hi)
+{
+  const guint32 vmax = (1u << depth) - 1u;
+
+  awb->gain[0] = p->gain[0];
+  awb->gain[1] = p->gain[2];
+  *lo = MAX (p->black_level, 1u);
+  *hi = vmax - (vmax >> 4);
+}
+
+/* One step of the loop on the 1 x 1 statistics of a frame: the targets are green-gain x the grey-world gains of the
+ * frame, and each gain moves by awb-speed x (target - gain).  TRUE with the stage to use from now on in `out`; FALSE
+ * when nothing changes (the helper found no usable mean, or the new matrix would leave its range). */
+static G_GNUC_UNUSED gboolean
+gst_mi_awb_step (const GstMiColourProps * p, GstMiAwb * awb, const mibayer_stats_zone * zone, gint pattern,
+    mibayer_colour * out)
+{
+  const double black[3] = { p->black_level, p->black_level, p->black_level };
+  double gw[3];
+  GstMiColourProps q = *p;      /* shares the ccm string: not cleared */
+  gchar *why = NULL;
+  gint k;
+
+  if (!mibayer_stats_grey_world || mibayer_stats_grey_world (zone, 1, pattern, black, gw) != 1)
+    return FALSE;
+  for (k = 0; k < 2; k++) {
+    const gdouble g = awb->gain[k] + p->awb_speed * (p->gain[1] * gw[2 * k] - awb->gain[k]);
+    q.gain[2 * k] = CLAMP (g, 0.0, 15.99);
+  }
+  if (!gst_mi_colour_props_build (&q, out, &why)) {
+    g_free (why);
+    return FALSE;
+  }
+  awb->gain[0] = q.gain[0];
+  awb->gain[1] = q.gain[2];
+  return TRUE;
+}
+
 static void
 gst_mi_colour_install_properties (GObjectClass * object_class, guint first)
 {
@@ -182,6 +269,16 @@ gst_mi_colour_install_properties (GObjectClass * object_class, guint first)
       g_param_spec_double ("gamma", "Gamma",
           "Exponent of tone-curve=gamma: out = in^(1/gamma)", 0.01, 100.0,
           GST_MI_COLOUR_DEFAULT_GAMMA, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_WHITE_BALANCE,
+      g_param_spec_enum ("white-balance", "White balance",
+          "manual: the gain properties as they are; grey-world: turns the colour stage on, measures "
+          "every frame and moves red-gain / blue-gain (the starting values) towards green-gain x the "
+          "grey-world gains of the frame, for the frames accepted afterwards",
+          gst_mi_colour_white_balance_get_type (), GST_MI_WHITE_BALANCE_MANUAL, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_AWB_SPEED,
+      g_param_spec_double ("awb-speed", "AWB speed",
+          "white-balance=grey-world: gain += awb-speed x (target - gain) after every frame; 1 = jump",
+          G_MINDOUBLE, 1.0, GST_MI_COLOUR_DEFAULT_AWB_SPEED, flags));
 }
 
 /* TRUE when `id` (relative to the element's first colour id) is a colour property; the caller holds its lock */
@@ -206,6 +303,12 @@ gst_mi_colour_set_property (GstMiColourProps * p, gint id, const GValue * value)
       return TRUE;
     case GST_MI_COLOUR_PROP_GAMMA:
       p->gamma = g_value_get_double (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_WHITE_BALANCE:
+      p->white_balance = g_value_get_enum (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AWB_SPEED:
+      p->awb_speed = g_value_get_double (value);
       return TRUE;
     default:
       return FALSE;
@@ -232,6 +335,12 @@ gst_mi_colour_get_property (const GstMiColourProps * p, gint id, GValue * value)
       return TRUE;
     case GST_MI_COLOUR_PROP_GAMMA:
       g_value_set_double (value, p->gamma);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_WHITE_BALANCE:
+      g_value_set_enum (value, p->white_balance);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AWB_SPEED:
+      g_value_set_double (value, p->awb_speed);
       return TRUE;
     default:
       return FALSE;

@@ -826,6 +826,15 @@ typedef struct
   gint method;                  /* property "method" (HB2R_METHOD_*; g_atomic_int_*), read when a context is made */
   gboolean ctx_single_shape;    /* the context runs the MHC or the colour kernel: one kernel shape, no plan to measure */
   GstMiColourProps colour;      /* the colour-stage properties (object lock), read when a context is made */
+  /* white-balance=grey-world (gstmicolour.h), set up with the context: the properties as latched then, the gains in
+   * use, the sample range, and ONE measurement in flight -- a zone in device memory, its pinned copy and the event
+   * behind the download, polled before every launch (never waited for while streaming) */
+  gboolean awb_on;
+  GstMiColourProps awb_props;
+  GstMiAwb awb;
+  guint32 awb_lo, awb_hi;
+  gpointer awb_d, awb_h, awb_ev;
+  gboolean awb_pending;
   gboolean prerolled;           /* a frame has left since start / flush: batching may begin */
   GQueue waiting;               /* Hb2rPair* */
   GQueue ready;                 /* GstBuffer* */
@@ -876,9 +885,56 @@ G_DEFINE_TYPE (GstMiHipBayer2RGB, gst_mi_hip_bayer2rgb, GST_TYPE_BASE_TRANSFORM)
     GST_CAPS_FEATURE_MEMORY_HIP, \
     "{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }")
 
+/* white-balance=grey-world: the measurement and its state go with the context (whose device they live on) */
+static void
+hb2r_awb_drop (GstMiHipBayer2RGB * self)
+{
+  if (self->awb_ev) {
+    if (self->awb_pending)
+      (void) mibayer_dev_event_wait (self->ctx_device, self->awb_ev);
+    mibayer_dev_event_destroy (self->ctx_device, self->awb_ev);
+  }
+  if (self->awb_d)
+    mibayer_dev_free (self->ctx_device, self->awb_d);
+  if (self->awb_h)
+    mibayer_host_free (self->awb_h);
+  self->awb_ev = self->awb_d = self->awb_h = NULL;
+  self->awb_pending = self->awb_on = FALSE;
+  gst_mi_colour_props_clear (&self->awb_props);
+}
+
+/* The zone of an earlier frame has arrived: one step of the gains, for the launches from now on.  Only polls. */
+static void
+hb2r_awb_poll (GstMiHipBayer2RGB * self)
+{
+  mibayer_colour colour;
+
+  if (!self->awb_pending || mibayer_dev_event_query (self->ctx_device, self->awb_ev) == 0)
+    return;
+  self->awb_pending = FALSE;
+  if (gst_mi_awb_step (&self->awb_props, &self->awb, (const mibayer_stats_zone *) self->awb_h, self->format, &colour))
+    (void) mibayer_set_colour (self->ctx, &colour);
+}
+
+/* Measure the mosaic at `d_src` behind the launch that has just been queued on `stream` (the frame's memories are
+ * marked after this, so the read is covered), unless a measurement is still on its way. */
+static void
+hb2r_awb_measure (GstMiHipBayer2RGB * self, const void *d_src, gpointer stream)
+{
+  if (!self->awb_on || self->awb_pending)
+    return;
+  if (mibayer_stats_device (self->ctx, d_src, 0, 1, 1, 1, self->awb_lo, self->awb_hi,
+          (mibayer_stats_zone *) self->awb_d, stream) == MIBAYER_OK
+      && mibayer_dev_download_async (self->ctx_device, self->awb_h, self->awb_d, sizeof (mibayer_stats_zone),
+          stream) == MIBAYER_OK
+      && mibayer_dev_event_record (self->ctx_device, self->awb_ev, stream) == MIBAYER_OK)
+    self->awb_pending = TRUE;
+}
+
 static void
 hb2r_drop_ctx (GstMiHipBayer2RGB * self)
 {
+  hb2r_awb_drop (self);
   if (self->launch_ev) {
     mibayer_dev_event_destroy (self->launch_ev_device, self->launch_ev);
     self->launch_ev = NULL;
@@ -1146,7 +1202,7 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
 {
   mibayer_cfg cfg;
   mibayer_colour colour;
-  gboolean want_colour = FALSE;
+  gboolean want_colour = FALSE, want_awb = FALSE;
   int rc;
 
   if (self->ctx != NULL && self->ctx_device == device)
@@ -1160,7 +1216,16 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
     want_colour = !gst_mi_colour_props_are_default (&self->colour);
     if (want_colour)
       ok = gst_mi_colour_props_build (&self->colour, &colour, &why) && mibayer_set_colour != NULL;
+    want_awb = ok && want_colour && self->colour.white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD;
+    if (want_awb) {
+      gst_mi_colour_props_copy (&self->awb_props, &self->colour);
+      gst_mi_awb_start (&self->awb_props, &self->awb, 8, &self->awb_lo, &self->awb_hi);
+    }
     GST_OBJECT_UNLOCK (self);
+    if (want_awb && (!mibayer_stats_device || !mibayer_stats_grey_world)) {
+      ok = FALSE;
+      why = g_strdup ("white-balance=grey-world: this libmibayer has no mosaic statistics");
+    }
     if (!ok) {
       GST_ELEMENT_ERROR (self, LIBRARY, SETTINGS,
           ("%s: cannot set up the colour stage", HB2R_LABEL (self)),
@@ -1201,6 +1266,19 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
     return FALSE;
   }
   self->ctx_device = device;
+  if (want_awb) {
+    self->awb_d = mibayer_dev_alloc (device, sizeof (mibayer_stats_zone));
+    self->awb_h = mibayer_host_alloc (sizeof (mibayer_stats_zone));
+    self->awb_ev = mibayer_dev_event_create (device);
+    if (!self->awb_d || !self->awb_h || !self->awb_ev) {
+      hb2r_drop_ctx (self);
+      GST_ELEMENT_ERROR (self, RESOURCE, FAILED,
+          ("%s: cannot set up white-balance=grey-world", HB2R_LABEL (self)),
+          ("no memory for the statistics zone: %s", mibayer_last_hip_error ()));
+      return FALSE;
+    }
+    self->awb_on = TRUE;
+  }
   self->tl_stream = mibayer_ctx_stream (self->ctx);
   self->tl = gst_mi_hip_timeline_for (device, self->tl_stream);
   self->tuned = FALSE;
@@ -1441,10 +1519,12 @@ hb2r_transform (GstBaseTransform * trans, GstBuffer * inbuf, GstBuffer * outbuf)
 
     hb2r_autotune_once (self, &one_src, &one_dst, 1);
   }
+  hb2r_awb_poll (self);
   /* device-resident call: no PCIe traffic at all */
   rc = mibayer_process_device (self->ctx, in_map.data, 0, out_map.data, 0, 1,
       stream);
   if (rc == MIBAYER_OK) {
+    hb2r_awb_measure (self, in_map.data, stream);
     if (tl) {
       gst_mi_hip_memory_mark_access_tl ((GstMiHipMemory *) in_mem, tl);
       gst_mi_hip_memory_mark_access_tl ((GstMiHipMemory *) out_mem, tl);
@@ -1518,9 +1598,12 @@ hb2r_convert_waiting (GstMiHipBayer2RGB * self)
   }
   if (ret == GST_FLOW_OK && n >= (guint) MIN (MAX (g_atomic_int_get (&self->batch), 1), HB2R_MAX_BATCH))
     hb2r_autotune_once (self, srcs, dsts, n);   /* on a full batch: what the steady state launches */
+  hb2r_awb_poll (self);
   rc = ret == GST_FLOW_OK
       ? mibayer_process_device_list (self->ctx, srcs, dsts, (int) n, stream)
       : MIBAYER_OK;
+  if (rc == MIBAYER_OK && ret == GST_FLOW_OK)
+    hb2r_awb_measure (self, srcs[0], stream);   /* the first frame of the batch */
   /* 2 n counter increments; whoever needs a fence behind this launch records ONE for all 2 n memories */
   for (i = 0; i < n && rc == MIBAYER_OK; i++) {
     gst_mi_hip_memory_mark_access_tl ((GstMiHipMemory *) in_mem[i], tl);

@@ -66,6 +66,7 @@ extern "C" {
  * was added, and a cfg without them means what it meant.  Likewise MIBAYER_FLAG_MHC (Malvar-He-Cutler demosaic). */
 /* 5, later additive: the fused colour stage -- MIBAYER_FLAG_COLOUR, struct mibayer_colour and the entry points of
  * group `colour`; a cfg without the flag means what it meant. */
+/* 5, later additive: mosaic zone statistics -- struct mibayer_stats_zone and the entry points of group `stats`. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -100,6 +101,9 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group stats: the ISP statistics block -- per-zone sums and counts per CFA site of the mosaic, and grey-world white balance
+ *     mibayer_stats_device mibayer_set_stats mibayer_frame_stats mibayer_pool_set_stats mibayer_pool_frame_stats
+ *     mibayer_stats_grey_world
  * group colour: the opt-in colour stage fused into the demosaic (MIBAYER_FLAG_COLOUR): black level, matrix, tone curve
  *     mibayer_colour_init mibayer_set_colour mibayer_get_colour mibayer_pool_set_colour mibayer_colour_matrix
  *     mibayer_colour_tone
@@ -290,6 +294,57 @@ int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour *colour);
 int mibayer_colour_matrix (const double gains[3], const double ccm[9], int32_t out[9]);
 /* tone[i] = round (65536 f (i / 256)) for MIBAYER_TONE_*; `gamma` is read by MIBAYER_TONE_GAMMA only */
 int mibayer_colour_tone (int curve, double gamma, uint32_t tone[257]);
+
+/* ---- mosaic zone statistics (additive within version 5: a struct and the entry points of group `stats`) -------- */
+
+/* What an ISP's statistics block hands to auto white balance and exposure: sums and counts per CFA site over a grid of
+ * zones, measured on the MOSAIC (before the demosaic and the colour stage) by a read-only kernel.
+ *   sample   S = what the deep path reads: the byte of an 8-bit mosaic, or the 16-bit word in the context's byte order
+ *            masked to `bits`; depth = 8 or `bits`, max = 2^depth - 1
+ *   site     s = 2 (y & 1) + (x & 1); its colour by Bayer order: bggr B G G R, gbrg G B R G, grbg G R B G, rggb R G G B
+ *   zones    a grid of zones_x x zones_y, each 1 .. 64, zones_x <= W/2 and zones_y <= H/2; a cell is
+ *            cw = 2 ceil ((W/2) / zones_x) pixels wide and ch = 2 ceil ((H/2) / zones_y) rows high (H/2 exact, not
+ *            rounded down: the last row of an odd height has a zone), pixel (x, y) belongs to zone (x / cw, y / ch);
+ *            trailing zones may be empty and are then all zero
+ * Only columns < W count: stride padding and the bits above `bits` are ignored.  Everything is an integer, so the result
+ * does not depend on the order of the kernel's atomic additions. */
+typedef struct mibayer_stats_zone {     /* 64 bytes */
+  uint64_t sum[4];              /* sum of S over the samples of site s with lo <= S <= hi */
+  uint32_t count[4];            /* their number */
+  uint32_t clipped[4];          /* samples of site s with S > hi */
+} mibayer_stats_zone;
+#define MIBAYER_STATS_MAX_ZONES 64      /* per direction */
+
+/* Device path: zeroes d_stats (nframes * zones_y * zones_x zones, frame-major, then row-major) on `hip_stream`, then
+ * ONE launch over the batch, frame f read at d_src + f * src_frame_bytes as by mibayer_process_device.  Valid on every
+ * bayer2rgb context (8-bit, deep, MHC, COLOUR).  MIBAYER_ERR_ARG on an RGB2BAYER context, lo > hi, hi > max, a grid
+ * outside the rule above, d_src not a multiple of 4 or d_stats not a multiple of 8; MIBAYER_ERR_GEOMETRY for a frame
+ * pitch as in mibayer_process_device.  Covered by mibayer_sync when launched on the context's stream. */
+int mibayer_stats_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, int nframes, int zones_x,
+    int zones_y, uint32_t lo, uint32_t hi, mibayer_stats_zone *d_stats, void *hip_stream);
+/* Host path: every frame accepted (mibayer_submit / mibayer_process_host) after this returns also gets its statistics,
+ * computed on the device copy of the mosaic that its ring slot holds anyway -- every row once, however many bands the
+ * frame is launched in -- and downloaded with the frame into pinned memory of the slot.  (0, 0) switches them off again
+ * (the default).  The converted bytes are the same with and without.  While statistics are on, a MIBAYER_FLAG_HIPGRAPH
+ * context launches without graphs.  Arguments as above. */
+int mibayer_set_stats (mibayer_ctx *ctx, int zones_x, int zones_y, uint32_t lo, uint32_t hi);
+/* The zones (row-major; nzones = zones_x * zones_y as the frame was accepted with) of the frame most recently handed
+ * back by mibayer_wait / mibayer_process_host; MIBAYER_ERR_EMPTY before the first such frame or when that frame was
+ * accepted with statistics off, MIBAYER_ERR_ARG when nzones is not its zone count.  Call it from the thread that
+ * retires the context's frames. */
+int mibayer_frame_stats (mibayer_ctx *ctx, mibayer_stats_zone *out, int nzones);
+/* ... of a pool: the grid of the frames mibayer_pool_submit accepts after it returns; the pool keeps the grid and the
+ * zones with each frame, as it keeps the colour stage.  mibayer_pool_frame_stats returns those of the frame
+ * mibayer_pool_wait handed back last, whichever shard converted it, also after a failover; a frame returned as lost
+ * (MIBAYER_ERR_TIMEOUT) has none (MIBAYER_ERR_EMPTY). */
+int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zones_y, uint32_t lo, uint32_t hi);
+int mibayer_pool_frame_stats (mibayer_pool *pool, mibayer_stats_zone *out, int nzones);
+/* Grey-world white balance from zones (pure host code, no device): all zones pooled per colour (both green sites into
+ * G), m_k = (double) S_k / (double) N_k - black[k] (black may be NULL = 0).  Any N_k == 0 or m_k <= 0: gains = (1, 1, 1),
+ * returns 0.  Else gains = (m_G / m_R, 1, m_G / m_B), each clamped to [1/16, 15.99], returns 1.  MIBAYER_ERR_ARG for a
+ * NULL pointer, nzones < 1 or a pattern that is no mibayer_pattern. */
+int mibayer_stats_grey_world (const mibayer_stats_zone *zones, int nzones, int pattern, const double black[3],
+    double gains[3]);
 
 /* ---- global ------------------------------------------------------------- */
 
