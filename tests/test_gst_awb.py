@@ -2,7 +2,8 @@
 a strong colour cast and awb-speed=1, compared byte for byte with the colour model (tests/colour_model.py) under the
 gains the loop must hold: the red-gain / blue-gain properties for the first frame, green-gain x the grey-world gains
 of the frame (tests/stats_model.py, 1 x 1 zones, lo = max(black-level, 1), hi = 255 - (255 >> 4)) once a measurement
-has been used.  white-balance=manual, spelled out, still gives the reference's recorded bytes."""
+has been used.  One test runs the loop below awb-speed=1 (0.5, and the default 0.25) and follows every step of it.
+white-balance=manual, spelled out, still gives the reference's recorded bytes."""
 import hashlib
 
 import numpy as np
@@ -47,6 +48,34 @@ def test_bayer2rgb_synchronous_follows_every_frame(plugin, gpu_pkg, tmp_path):
     assert np.array_equal(got[0], manual)
     for i in range(1, n):
         assert np.array_equal(got[i], grey), i
+
+
+@pytest.mark.parametrize("speed", [0.5, None], ids=["0.5", "default"])
+def test_bayer2rgb_synchronous_moves_by_awb_speed(plugin, gpu_pkg, tmp_path, speed):
+    """awb-speed below 1 (None: the property left out, 0.25): frame 0 under the manual gains, frame i under
+    g_i = g_(i-1) + s (green_gain x gw - g_(i-1)), in doubles and in the operation order of gst_mi_awb_step"""
+    w, h, n = 320, 50, 5
+    src = cast_frames(w, h, n, 1)
+    s = 0.25 if speed is None else speed
+    props = PROPS.replace(" awb-speed=1", "" if speed is None else " awb-speed=%g" % speed)
+    assert ("awb-speed" in props) == (speed is not None) and "grey-world" in props
+    zones = sm.zone_stats(sm.samples(src[0], w, h, w), 1, 1, max(BLACK, 1), 255 - (255 >> 4))
+    ok, gw = sm.grey_world(zones, "rggb", (BLACK,) * 3)
+    assert ok == 1
+    gains = [(MANUAL[0], MANUAL[2])]
+    for _ in range(1, n):
+        gains.append(tuple(min(max(g + s * (MANUAL[1] * gw[2 * k] - g), 0.0), 15.99) for k, g in enumerate(gains[-1])))
+    # the quantised matrix of every step does not hang on the last bit of a gain
+    matrices = [gpu_pkg.colour_matrix((r, MANUAL[1], b), None) for r, b in gains]
+    for (r, b), m in zip(gains, matrices):
+        for r2 in (np.nextafter(r, -np.inf), np.nextafter(r, np.inf)):
+            for b2 in (np.nextafter(b, -np.inf), np.nextafter(b, np.inf)):
+                assert gpu_pkg.colour_matrix((float(r2), MANUAL[1], float(b2)), None) == m
+    want = [cm.bayer2rgb_colour(src[0], w, h, "rggb", "BGRx", black=(BLACK,) * 3, matrix=m) for m in matrices]
+    assert all(not np.array_equal(want[i], want[j]) for i in range(n) for j in range(i))    # the loop cannot be frozen
+    got = file_pipeline(tmp_path, src, w, h, "rggb", "BGRx", 4, props, "awbs")
+    for i in range(n):
+        assert np.array_equal(got[i], want[i]), i
 
 
 def test_bayer2rgb_queued_converges(plugin, gpu_pkg, tmp_path):
