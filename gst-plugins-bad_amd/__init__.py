@@ -39,6 +39,8 @@ FORMATS = {
 # 16-bit-per-channel output (MIBAYER_FLAG_DST_16BIT): (r_off, g_off, b_off) in 16-bit CHANNELS of the 8-byte pixel.
 # ARGB64 is the one the GStreamer video library of the element knows; the other three are the same layouts as above
 FORMATS16 = {"ARGB64": (1, 2, 3), "RGBA64": (0, 1, 2), "BGRA64": (2, 1, 0), "ABGR64": (3, 2, 1)}
+# packed 24-bit output (MIBAYER_FLAG_DST_24BIT): byte offsets inside the 3-byte pixel -- RGBx / BGRx without byte 3
+FORMATS24 = {"RGB": (0, 1, 2), "BGR": (2, 1, 0)}
 SRC_BITS = (10, 12, 14, 16)     # MIBAYER_FLAG_SRC_BITS(n) values besides 0 (the 8-bit mosaic)
 
 PLAN_DEFAULT, PLAN_MEASURED, PLAN_CACHED, PLAN_SET = 0, 1, 2, 3
@@ -84,6 +86,7 @@ FLAG_SRC_BITS_MASK = 0x1F << 8
 FLAG_SRC_BIG_ENDIAN = 1 << 13
 FLAG_DST_16BIT = 1 << 14
 FLAG_DST_BIG_ENDIAN = 1 << 15
+FLAG_DST_24BIT = 1 << 21        # 3-byte pixels, RGB / BGR; dst_stride defaults to ROUND_UP_4(3 * width)
 FLAG_MHC = 1 << 16              # Malvar-He-Cutler demosaic instead of the reference's bilinear one
 METHODS = {"bilinear": 0, "mhc": FLAG_MHC}      # the `method` keyword of make_cfg / Context / Pool
 FLAG_COLOUR = 1 << 19           # fused colour stage: black level, Q12 matrix, tone curve (struct mibayer_colour)
@@ -367,7 +370,8 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
              inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False,
              method="bilinear", colour=None):
     """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
-    name implies out16.  method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
+    name implies out16, a FORMATS24 name ("RGB", "BGR") FLAG_DST_24BIT.  method: "bilinear" (the reference's,
+    bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
     colour: None / False = no colour stage; True or a Colour = FLAG_COLOUR (Context / Pool apply the Colour)"""
     if colour is not None and colour is not False:
         flags |= FLAG_COLOUR
@@ -377,6 +381,9 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
     if isinstance(fmt, str) and fmt in FORMATS16:
         out16 = True
         r, g, b = FORMATS16[fmt]
+    elif isinstance(fmt, str) and fmt in FORMATS24:
+        flags |= FLAG_DST_24BIT
+        r, g, b = FORMATS24[fmt]
     else:
         r, g, b = FORMATS[fmt] if isinstance(fmt, str) else fmt
     flags |= deep_flags(bits, src_big_endian, out16, dst_big_endian)
@@ -512,7 +519,7 @@ class Context:
         self.src_bytes = out.src_stride * out.height
         self.dst_bytes = out.dst_stride * out.height
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
-        self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT))
+        self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT | FLAG_DST_24BIT))
         self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
         self.colour = bool(out.flags & FLAG_COLOUR)
         self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on

@@ -821,6 +821,7 @@ static void make_deep_plan (mibayer_ctx *c)
   q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
   q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
   q.out_shift = c->kind.out16 ? 16 - depth : depth - 8;
+  q.px3 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
   if (c->kind.mhc || c->colour)
     make_cgd_selectors (c, depth);
   for (int k = 0; k < 4; k++)
@@ -1212,7 +1213,7 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   if (f.pattern < MIBAYER_BGGR || f.pattern > MIBAYER_RGGB)
     return MIBAYER_ERR_ARG;
   constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
-      | MIBAYER_FLAG_DST_BIG_ENDIAN;
+      | MIBAYER_FLAG_DST_BIG_ENDIAN | MIBAYER_FLAG_DST_24BIT;
   if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags
           | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
@@ -1227,6 +1228,8 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     return MIBAYER_ERR_ARG;
   if ((f.flags & MIBAYER_FLAG_DST_BIG_ENDIAN) && !(f.flags & MIBAYER_FLAG_DST_16BIT))
     return MIBAYER_ERR_ARG;
+  if ((f.flags & MIBAYER_FLAG_DST_24BIT) && (f.flags & MIBAYER_FLAG_DST_16BIT))
+    return MIBAYER_ERR_ARG;                     /* 3-byte pixels have 8-bit channels */
   if ((f.flags & MIBAYER_FLAG_HIPGRAPH_CHAIN) && !(f.flags & MIBAYER_FLAG_HIPGRAPH))
     return MIBAYER_ERR_ARG;
   if (f.flags & MIBAYER_FLAG_RGB2BAYER) {
@@ -1268,17 +1271,21 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   /* deep samples: 2 B per sample, 8 B per output pixel (16-bit rows of a width this large would pass 2^31 bytes) */
   const int src_row = src_bits ? 2 * f.width : (f.width + 3) & ~3;
   const bool dst16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
-  if ((src_bits || dst16) && f.width > (1 << 26))
+  const bool dst24 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
+  if ((src_bits || dst16 || dst24) && f.width > (1 << 26))
     return MIBAYER_ERR_GEOMETRY;
+  const int dst_px = dst16 ? 8 : dst24 ? 3 : 4;
   if (f.src_stride == 0)
     f.src_stride = src_row;             /* GST_ROUND_UP_4, gstbayer2rgb.c:477 */
-  if (f.dst_stride == 0)
-    f.dst_stride = (dst16 ? 8 : 4) * f.width;   /* gstbayer2rgb.c:344 */
+  if (f.dst_stride == 0)                /* gstbayer2rgb.c:344; 3-byte pixels: GStreamer's RGB stride, ROUND_UP_4 (3 w) */
+    f.dst_stride = (dst_px * f.width + 3) & ~3;
   if (f.src_stride < src_row || (f.src_stride & 3))
     return MIBAYER_ERR_GEOMETRY;
-  if (f.dst_stride < (dst16 ? 8 : 4) * f.width || (f.dst_stride & (dst16 ? 7 : 3)))
+  if (f.dst_stride < dst_px * f.width || (f.dst_stride & (dst16 ? 7 : 3)))
     return MIBAYER_ERR_GEOMETRY;
-  if (!layout_known (f.r_off, f.g_off, f.b_off))
+  /* 3-byte pixels: RGB or BGR -- the bytes of RGBx / BGRx without the fourth, so the selectors are those layouts' */
+  if (dst24 ? !(f.g_off == 1 && ((f.r_off == 0 && f.b_off == 2) || (f.r_off == 2 && f.b_off == 0)))
+      : !layout_known (f.r_off, f.g_off, f.b_off))
     return MIBAYER_ERR_LAYOUT;
   if (f.inflight == 0)
     f.inflight = 2;
@@ -1413,7 +1420,8 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
     mibayer_colour_init (&c->colour_user);
     (void) colour_stage_from (&c->colour_user, &c->colour_stage);
   }
-  c->deep = c->kind.mhc || c->colour || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT)) != 0;
+  c->deep = c->kind.mhc || c->colour
+      || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1745,8 +1753,8 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   int rc = validate (cfg, &f);
   if (rc != MIBAYER_OK)
     return rc;
-  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_MHC
-          | MIBAYER_FLAG_COLOUR))
+  if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT
+          | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -1782,6 +1790,8 @@ extern "C" const char *mibayer_ctx_variant_name (const mibayer_ctx *c)
     return c->kind.mhc ? "colour_mhc_256x16" : "colour_bilinear_256x16";
   if (c && c->kind.mhc)
     return "mhc_256x16";
+  if (c && c->deep)             /* the bilinear strip kernel: it has no entry in the variant table */
+    return "deep_256x16";
   return c ? c->plan[PLAN_BATCH].var->name : NULL;
 }
 
@@ -2349,7 +2359,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 static size_t written_row_bytes (const mibayer_ctx *c)
 {
   return c->inverse ? (size_t) ((c->cfg.width + 3) & ~3)
-      : (size_t) (c->kind.out16 ? 8 : 4) * c->cfg.width;
+      : (size_t) (c->kind.out16 ? 8 : (c->cfg.flags & MIBAYER_FLAG_DST_24BIT) ? 3 : 4) * c->cfg.width;
 }
 
 static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
@@ -3672,8 +3682,9 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     size_t src_frame_bytes, uint32_t first_frame, int nframes, uint32_t seed,
     void *hip_stream)
 {
-  /* the generator writes 8-bit mosaics: an MHC context of one takes it, no other deep context does */
-  if (!c || !d_src || nframes < 0 || c->inverse || (c->deep && !((c->kind.mhc || c->colour) && c->kind.in8)))
+  /* the generator writes 8-bit mosaics: an MHC, colour or 24-bit context of one takes it, no other deep context does */
+  if (!c || !d_src || nframes < 0 || c->inverse
+      || (c->deep && !((c->kind.mhc || c->colour || c->deep_args.px3) && c->kind.in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

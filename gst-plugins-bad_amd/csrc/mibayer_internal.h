@@ -257,6 +257,8 @@ struct DeepParams {
   int vmax;                     /* 2^depth - 1 */
   uint32_t sel_cgd[2][2];       /* [row: 0 = its non-green colour is R, 1 = B][output dword], v_perm selectors over
                                    {x = [C, G], y = [D, 0]} at output depth; 4-byte output uses [.][0] only */
+  int px3;                      /* 8-bit channels only: 3-byte pixels (MIBAYER_FLAG_DST_24BIT), the selectors those of
+                                   RGBx / BGRx and byte 3 dropped at the store (store_strip8) */
   /* filled by launch_strip */
   int groups;                   /* 4-pixel groups per row = ceil (width / 4) */
   FastDiv div_tiles_x;          /* 256-pixel strips per row */
@@ -290,7 +292,8 @@ struct ColourParams {
 struct StripKind { bool mhc, in8, out16; };
 /* One launch of a strip kernel over chunks [chunk0, chunk0 + nchunks) of the batch (nchunks < 0: all of p.nlist frames,
  * or of `nframes`).  stage = NULL: bayer2rgb_deep_kernel / bayer2rgb_mhc_kernel of the kind; bilinear 8-bit mosaic to
- * 4-byte pixels is refused (the production kernels serve it).  Otherwise bayer2rgb_colour_kernel with that stage: one
+ * 4-byte pixels is refused (the production kernels serve it; to 3-byte pixels, p.px3, it is the deep kernel's).
+ * Otherwise bayer2rgb_colour_kernel with that stage: one
  * kernel for both demosaic methods and all four input / output combinations (uniform run-time branches) */
 hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1);

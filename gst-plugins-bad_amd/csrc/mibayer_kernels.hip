@@ -51,6 +51,7 @@ typedef uint32_t u32x2 __attribute__ ((ext_vector_type (2)));
  * instruction through these instead of dword by dword */
 typedef uint32_t u32x4_a4 __attribute__ ((ext_vector_type (4), aligned (4)));
 typedef uint32_t u32x2_a4 __attribute__ ((ext_vector_type (2), aligned (4)));
+typedef uint32_t u32x3_a4 __attribute__ ((ext_vector_type (3), aligned (4)));   /* a store writes 12 bytes */
 
 /* ------------------------------------------------------------------------- */
 /* packed-byte primitives                                                     */
@@ -1593,10 +1594,23 @@ __device__ __forceinline__ void deep_quad_pieces (u32x4 v0, u32x4 v1, int k, u32
 }
 
 /* 4-byte pixels of group g: four as one streaming 16-byte store, the two of a width % 4 == 2 tail (!full) as 8 bytes;
- * store = the group is inside the row */
-__device__ __forceinline__ void store_strip8 (uint8_t *out, int g, bool store, bool full, u32x4 v)
+ * store = the group is inside the row.  px3 (wave-uniform, MIBAYER_FLAG_DST_24BIT): byte 3 of every pixel is dropped --
+ * the layouts are RGBx / BGRx, so three fixed v_perm_b32 close the gaps -- and the group is 12 bytes at out + 12 g, one
+ * streaming store; the tail is 6 bytes, a dword and a 16-bit store, and not a byte more (the row may end there) */
+__device__ __forceinline__ void store_strip8 (uint8_t *out, int g, bool store, bool full, bool px3, u32x4 v)
 {
-  if (store) {
+  if (store && px3) {
+    uint8_t *q = out + 12 * (size_t) g;
+    const uint32_t d0 = __builtin_amdgcn_perm (v.y, v.x, 0x04020100u);
+    const uint32_t d1 = __builtin_amdgcn_perm (v.z, v.y, 0x05040201u);
+    if (full) {
+      const u32x3_a4 three = { d0, d1, __builtin_amdgcn_perm (v.w, v.z, 0x06050402u) };
+      __builtin_nontemporal_store (three, (u32x3_a4 *) q);
+    } else {
+      __builtin_nontemporal_store (d0, (uint32_t *) q);
+      __builtin_nontemporal_store ((uint16_t) d1, (uint16_t *) (q + 4));
+    }
+  } else if (store) {
     uint8_t *q = out + 16 * (size_t) g;
     if (full) {
       __builtin_nontemporal_store (v, (u32x4_a4 *) q);
@@ -1720,7 +1734,7 @@ bayer2rgb_deep_kernel (DeepParams p)
       v.y = __builtin_amdgcn_perm (m_lo, gw, p.sel[1]);
       v.z = __builtin_amdgcn_perm (m_hi, gw, p.sel[2]);
       v.w = __builtin_amdgcn_perm (m_hi, gw, p.sel[3]);
-      store_strip8 (out, g, store, full, v);
+      store_strip8 (out, g, store, full, p.px3 != 0, v);
     }
     up = cur;
     cur = dn;
@@ -1928,7 +1942,7 @@ bayer2rgb_mhc_kernel (DeepParams p)
       const uint32_t s0 = p.sel_cgd[rk][0];
       u32x4 v, unused;
       emit_cgd<false> (x, y, s0, s0, v, unused);
-      store_strip8 (out, g, store, full, v);
+      store_strip8 (out, g, store, full, p.px3 != 0, v);
     }
     w0 = w1;
     w1 = w2;
@@ -2150,7 +2164,7 @@ bayer2rgb_colour_kernel (ColourParams cp)
     } else {
       u32x4 vv, unused;
       emit_cgd<false> (x, y, s0, s0, vv, unused);
-      store_strip8 (out, g, store, full, vv);
+      store_strip8 (out, g, store, full, p.px3 != 0, vv);
     }
     w0 = w1;
     w1 = w2;
@@ -2194,10 +2208,10 @@ static hipError_t deep_grid (DeepParams &q, int nframes, long long chunk0, long 
 }
 
 typedef void (*StripFn) (DeepParams);
-/* [mhc][in8][out16]; bilinear 8 -> 8 is the production (LDS) kernels' */
+/* [mhc][in8][out16]; bilinear 8 -> 8 is the production (LDS) kernels' unless the pixels are 3 bytes (px3) */
 static const StripFn kStripKernels[2][2][2] = {
   { { bayer2rgb_deep_kernel<false, false>, bayer2rgb_deep_kernel<false, true> },
-    { nullptr, bayer2rgb_deep_kernel<true, true> } },
+    { bayer2rgb_deep_kernel<true, false>, bayer2rgb_deep_kernel<true, true> } },
   { { bayer2rgb_mhc_kernel<false, false>, bayer2rgb_mhc_kernel<false, true> },
     { bayer2rgb_mhc_kernel<true, false>, bayer2rgb_mhc_kernel<true, true> } },
 };
@@ -2206,7 +2220,9 @@ hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage 
     long long chunk0, long long nchunks)
 {
   const StripFn fn = kStripKernels[kind.mhc][kind.in8][kind.out16];
-  if (p.width < 4 || p.height < 3 || (p.width & 1) || (!stage && !fn))
+  if (p.width < 4 || p.height < 3 || (p.width & 1) || (p.px3 && kind.out16))
+    return hipErrorInvalidValue;
+  if (!stage && !kind.mhc && kind.in8 && !kind.out16 && !p.px3)        /* the production kernels' */
     return hipErrorInvalidValue;
   ColourParams q;               /* q.d alone is the argument of the plain kernels */
   q.d = p;

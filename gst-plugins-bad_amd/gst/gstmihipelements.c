@@ -824,7 +824,8 @@ typedef struct
   guint busy_run;               /* consecutive frames that arrived while the previous conversion was still running */
   gchar plan[160];              /* property "plan" (read-only): the context's launch plan and where it came from */
   gint method;                  /* property "method" (HB2R_METHOD_*; g_atomic_int_*), read when a context is made */
-  gboolean ctx_single_shape;    /* the context runs the MHC or the colour kernel: one kernel shape, no plan to measure */
+  gboolean ctx_single_shape;    /* the context runs the MHC, the colour or (24-bit output) the deep kernel: one kernel
+                                   shape, no plan to measure */
   GstMiColourProps colour;      /* the colour-stage properties (object lock), read when a context is made */
   /* white-balance=grey-world (gstmicolour.h), set up with the context: the properties as latched then, the gains in
    * use, the sample range, and ONE measurement in flight -- a zone in device memory, its pinned copy and the event
@@ -871,7 +872,11 @@ typedef struct
 #define HB2R_LABEL(obj) (HB2R_CLASS_OF (obj)->label)
 /* bytes of the element's input / output frame */
 #define HB2R_MOSAIC_BYTES(self) ((gsize) GST_ROUND_UP_4 ((self)->width) * (self)->height)
-#define HB2R_VIDEO_BYTES(self) ((gsize) 4 * (self)->width * (self)->height)
+/* 4-byte pixels, or packed RGB / BGR (hipbayer2rgb's second src structure) at GStreamer's stride ROUND_UP_4 (3 w) */
+#define HB2R_PX3(self) (!HB2R_INVERSE (self) && GST_VIDEO_INFO_N_COMPONENTS (&(self)->info) == 3 \
+    && GST_VIDEO_INFO_COMP_PSTRIDE (&(self)->info, 0) == 3)
+#define HB2R_VIDEO_BYTES(self) ((gsize) (HB2R_PX3 (self) ? GST_ROUND_UP_4 (3 * (self)->width) : 4 * (self)->width) \
+    * (self)->height)
 #define HB2R_IN_BYTES(self) (HB2R_INVERSE (self) ? HB2R_VIDEO_BYTES (self) : HB2R_MOSAIC_BYTES (self))
 #define HB2R_OUT_BYTES(self) (HB2R_INVERSE (self) ? HB2R_MOSAIC_BYTES (self) : HB2R_VIDEO_BYTES (self))
 
@@ -881,9 +886,12 @@ G_DEFINE_TYPE (GstMiHipBayer2RGB, gst_mi_hip_bayer2rgb, GST_TYPE_BASE_TRANSFORM)
 #define HB2R_SINK_CAPS HIP_CAPS ("video/x-bayer") \
   ",format=(string){bggr,grbg,gbrg,rggb}," \
   "width=(int)[1,MAX],height=(int)[1,MAX],framerate=(fraction)[0/1,MAX]"
+/* the second structure: packed 24-bit pixels (MIBAYER_FLAG_DST_24BIT), appended so that default negotiation keeps
+ * landing on RGBx */
 #define HB2R_SRC_CAPS GST_VIDEO_CAPS_MAKE_WITH_FEATURES ( \
     GST_CAPS_FEATURE_MEMORY_HIP, \
-    "{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }")
+    "{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }") "; " \
+    GST_VIDEO_CAPS_MAKE_WITH_FEATURES (GST_CAPS_FEATURE_MEMORY_HIP, "{ RGB, BGR }")
 
 /* white-balance=grey-world: the measurement and its state go with the context (whose device they live on) */
 static void
@@ -1085,13 +1093,18 @@ static gboolean
 hb2r_get_unit_size (GstBaseTransform * trans, GstCaps * caps, gsize * size)
 {
   GstStructure *s = gst_caps_get_structure (caps, 0);
+  const gchar *fmt = gst_structure_get_string (s, "format");
   gint w, h;
 
   if (!gst_structure_get_int (s, "width", &w)
       || !gst_structure_get_int (s, "height", &h))
     return FALSE;
-  *size = gst_structure_has_name (s, "video/x-raw") ? (gsize) w * h * 4
-      : (gsize) GST_ROUND_UP_4 (w) * h;
+  if (!gst_structure_has_name (s, "video/x-raw"))
+    *size = (gsize) GST_ROUND_UP_4 (w) * h;
+  else if (fmt && (g_str_equal (fmt, "RGB") || g_str_equal (fmt, "BGR")))
+    *size = (gsize) GST_ROUND_UP_4 (3 * w) * h;         /* what GstVideoInfo says of RGB / BGR */
+  else
+    *size = (gsize) w * h * 4;
   return TRUE;
 }
 
@@ -1248,7 +1261,11 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
     cfg.flags |= MIBAYER_FLAG_MHC;
   if (want_colour)
     cfg.flags |= MIBAYER_FLAG_COLOUR;
-  self->ctx_single_shape = (cfg.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR)) != 0;
+  if (HB2R_PX3 (self)) {        /* RGB / BGR: offsets 0,1,2 / 2,1,0 from GstVideoInfo, and its stride, said explicitly */
+    cfg.flags |= MIBAYER_FLAG_DST_24BIT;
+    cfg.dst_stride = GST_VIDEO_INFO_PLANE_STRIDE (&self->info, 0);
+  }
+  self->ctx_single_shape = (cfg.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR | MIBAYER_FLAG_DST_24BIT)) != 0;
   rc = mibayer_create (&cfg, &self->ctx);
   if (rc == MIBAYER_OK && want_colour && (rc = mibayer_set_colour (self->ctx, &colour)) != MIBAYER_OK) {
     mibayer_destroy (self->ctx);

@@ -67,6 +67,8 @@ extern "C" {
 /* 5, later additive: the fused colour stage -- MIBAYER_FLAG_COLOUR, struct mibayer_colour and the entry points of
  * group `colour`; a cfg without the flag means what it meant. */
 /* 5, later additive: mosaic zone statistics -- struct mibayer_stats_zone and the entry points of group `stats`. */
+/* 5, later additive: packed 24-bit output -- MIBAYER_FLAG_DST_24BIT, a fifth deep flag; no struct field and no entry
+ * point was added, and a cfg without the flag means what it meant. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -191,7 +193,8 @@ typedef struct mibayer_cfg {
 #define MIBAYER_FLAG_HIPGRAPH_CHAIN 4u
 
 /* Deep samples (additive within version 5: flags only, mibayer_cfg keeps its fields).  A context with any of the
- * four flags below is a DEEP context; the algorithm is the one of the 8-bit path on wider integers:
+ * four flags below, or MIBAYER_FLAG_DST_24BIT (a paragraph of its own further down), is a DEEP context; the algorithm
+ * is the one of the 8-bit path on wider integers:
  *   input   one 16-bit word per sample (little-endian; big-endian with MIBAYER_FLAG_SRC_BIG_ENDIAN), masked to its
  *           low `bits` bits -- everything above them is ignored; MIBAYER_FLAG_SRC_BITS(0) = the 8-bit mosaic;
  *   average avg(a,b) = (a+b+1)>>1 on the masked values, at the native depth; nothing is rescaled before the end;
@@ -215,6 +218,27 @@ typedef struct mibayer_cfg {
 #define MIBAYER_FLAG_SRC_BIG_ENDIAN (1u << 13)
 #define MIBAYER_FLAG_DST_16BIT (1u << 14)
 #define MIBAYER_FLAG_DST_BIG_ENDIAN (1u << 15)
+
+/* Packed 24-bit output (additive within version 5: a flag only): 3-byte pixels, RGB or BGR, what tensor preprocessing,
+ * encoders and image writers take -- no pad byte written, and no second pass to drop it.  A fifth deep flag: a context
+ * that carries it is a DEEP context and everything said of deep contexts above holds (one kernel shape, no plans, variant
+ * must be 0; MIBAYER_FLAG_HIPGRAPH is accepted and the host path runs without graphs; mibayer_autotune[_list],
+ * mibayer_set_plan[_for], mibayer_plan_selectors and mibayer_launch_geometry return MIBAYER_ERR_ARG), except that
+ * mibayer_fill_synthetic works when the mosaic is 8-bit; mibayer_ctx_variant_name names the strip kernel.
+ *   output  the R, G and B bytes of the SAME cfg with RGBx (0,1,2) or BGRx (2,1,0) and without the flag, byte 3 dropped:
+ *           the reference's bytes for an 8-bit mosaic, v >> (bits - 8) for deep mosaics, the MHC filters' and the colour
+ *           stage's o >> 8 alike.  (r_off, g_off, b_off) = (0,1,2) is RGB, (2,1,0) is BGR; anything else is
+ *           MIBAYER_ERR_LAYOUT.
+ *   strides dst_stride default ROUND_UP_4 (3*width), GStreamer's RGB stride; >= 3*width and a multiple of 4.  Only the
+ *           first 3*width bytes of a row are written, on the device paths and on the host path alike: with
+ *           width % 4 == 2 the row ends two bytes before the default stride, and those two bytes (like every byte of a
+ *           wider stride's padding) keep what they held.  Device pointers and frame pitches: multiples of 4, as above.
+ * Goes with MIBAYER_FLAG_SRC_BITS (10/12/14/16), _SRC_BIG_ENDIAN, MIBAYER_FLAG_MHC, MIBAYER_FLAG_COLOUR and the
+ * statistics; with MIBAYER_FLAG_DST_16BIT, _DST_BIG_ENDIAN or MIBAYER_FLAG_RGB2BAYER it is MIBAYER_ERR_ARG.  Geometry
+ * as the 8-bit path (even width >= 4, height >= 3), width <= 2^26 as for the other deep flags.  A plain 8-bit bilinear
+ * context with the flag runs the strip kernel instead of the production kernels; its bytes are theirs.  (Bit 21: bits
+ * 17, 18 and 20 stay unknown flags, MIBAYER_ERR_ARG, as they have been.) */
+#define MIBAYER_FLAG_DST_24BIT (1u << 21)
 
 /* Malvar-He-Cutler demosaic (additive within version 5: a flag only).  Instead of the reference's bilinear average, the
  * gradient-corrected linear interpolation of Malvar, He and Cutler (ICASSP 2004): fewer zipper artefacts and colour
