@@ -1147,7 +1147,9 @@ def test_sector_aligned_store_arm(gpu_lab_pkg, oracle, align, monkeypatch):
 def test_shifted_arm_through_set_plan(gpu_pkg, oracle):
     """The product build's way to the sector-aligned arm (no tuning environment): mibayer_set_plan (variant, band,
     128) -- what mibayer_autotune picks among and what the plan cache hands to later contexts -- on generic geometries
-    with guard bands; plans that do not exist (64-byte flavour, shapes without the arm) are refused."""
+    with guard bands; plans that do not exist (64-byte flavour, shapes without the arm) are refused.  (Every per-row
+    shift, narrow frames and both sides of the edge-wave test: ALIGNED_CASES of tests/tile_cases.py, run by
+    tests/test_gpu_tile_geometry.py.)"""
     rng = np.random.default_rng(2718)
     names = gpu_pkg.variant_names()
     guard = 2048
