@@ -33,7 +33,9 @@
  *     marches down its rows with a 3-row sliding window of (E,O) in registers;
  *   - the x-1 / x+4 neighbour bytes come from the adjacent lanes through DPP
  *     wave shifts (no memory traffic); only lanes 0 and 63 take theirs from LDS;
- *   - blockIdx -> tile is XCD-aware (mibayer_internal.h: block_to_tile).
+ *   - blockIdx -> tile is XCD-aware (mibayer_internal.h: block_to_tile; tile_of gives the tile's frame and origin).
+ * The tile kernels share TileShape (constants), tile_of, stage_rows_generic, edge_lines (the edge columns), march_rows
+ * and store_two; see "what the tile kernels share" below.
  * The op is a pure HBM stream (1 B read + 4 B written per pixel, ~25 integer
  * ops per 4 pixels): no MFMA.
  */
@@ -138,16 +140,13 @@ __device__ __forceinline__ uint32_t from_lane_above (uint32_t edge, uint32_t v)
 
 struct Lines { uint32_t e, o; };
 
-/* c  = S[x0..x0+3], cl = dword left of it, cr = dword right of it.
- * first: x0 == 0.   lastmode: 1 = this lane holds columns W-4..W-1,
- *                             2 = this lane holds columns W-2..W-1 only. */
-template <bool INTRIN, bool GENERIC>
-__device__ __forceinline__ Lines row_lines (uint32_t c, uint32_t cl,
-    uint32_t cr, bool first, int lastmode)
+/* (E,O) of the four columns c = S[x0..x0+3] from their x-1 / x+1 neighbour windows lsh = S[x0-1..x0+2] and
+ * rsh = S[x0+1..x0+4], with the frame's edge columns: the one place that states them.
+ * first: x0 == 0.   last4: this lane holds columns W-4..W-1.   last2: it holds columns W-2..W-1 only. */
+template <bool INTRIN>
+__device__ __forceinline__ Lines edge_lines (uint32_t lsh, uint32_t c,
+    uint32_t rsh, bool first, bool last4, bool last2)
 {
-  /* x-1 neighbours: [cl.3, c0, c1, c2];  x+1 neighbours: [c1, c2, c3, cr.0] */
-  uint32_t lsh = funnel_bytes<INTRIN> (c, cl, 3);
-  uint32_t rsh = funnel_bytes<INTRIN> (cr, c, 1);
   /* O[0] = S[1] (:361): make the left neighbour of column 0 equal S[1] */
   uint32_t lsh_first = (lsh & 0xffffff00u) | ((c >> 8) & 0xffu);
   lsh = first ? lsh_first : lsh;
@@ -155,14 +154,25 @@ __device__ __forceinline__ Lines row_lines (uint32_t c, uint32_t cl,
    * two columns are replaced by their left neighbours */
   uint32_t t = lsh >> 16;                    /* [c1, c2, 0, 0] */
   uint32_t rsh_last = t | (t << 16);          /* [c1, c2, c1, c2] */
-  rsh = (lastmode == 1) ? rsh_last : rsh;
-  if constexpr (GENERIC)
-    rsh = (lastmode == 2) ? lsh : rsh;        /* [L, c0, -, -] */
+  rsh = last4 ? rsh_last : rsh;
+  rsh = last2 ? lsh : rsh;                    /* [L, c0, -, -] */
   uint32_t a = avg4<INTRIN> (lsh, rsh);
   Lines r;
   r.e = bsel (kEvenBytes, c, a);
   r.o = bsel (kEvenBytes, a, c);
   return r;
+}
+
+/* c  = S[x0..x0+3], cl = dword left of it, cr = dword right of it.
+ * lastmode: 1 = this lane holds columns W-4..W-1, 2 = columns W-2..W-1 only (generic geometries). */
+template <bool INTRIN, bool GENERIC>
+__device__ __forceinline__ Lines row_lines (uint32_t c, uint32_t cl,
+    uint32_t cr, bool first, int lastmode)
+{
+  /* x-1 neighbours: [cl.3, c0, c1, c2];  x+1 neighbours: [c1, c2, c3, cr.0] */
+  uint32_t lsh = funnel_bytes<INTRIN> (c, cl, 3);
+  uint32_t rsh = funnel_bytes<INTRIN> (cr, c, 1);
+  return edge_lines<INTRIN> (lsh, c, rsh, first, lastmode == 1, GENERIC && lastmode == 2);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -196,6 +206,19 @@ __device__ __forceinline__ u32x4 merge_rows (const Lines &u, const Lines &c,
   return px;
 }
 
+/* the lane that holds the last two columns of a width % 4 == 2 frame writes two pixels, at dword alignment */
+template <bool NT>
+__device__ __forceinline__ void store_two (uint8_t *p, u32x4 px)
+{
+  u32x2 two;
+  two.x = px.x;
+  two.y = px.y;
+  if constexpr (NT)
+    __builtin_nontemporal_store (two, (u32x2_a4 *) p);
+  else
+    *(u32x2_a4 *) p = two;
+}
+
 /* ST = cache policy of the 16-byte output stores (the output is never re-read):
  * 0 plain, 1 nt (streaming hint), 2 sc1, 3 sc0 sc1 (write-through, line dropped
  * from the XCD L2), 4 nt sc1; + 8 = nt hint on the LDS kernel's row loads too,
@@ -218,20 +241,14 @@ __device__ __forceinline__ void store_pixels (uint8_t *p, u32x4 px,
       *(u32x4 *) p = px;
   } else {
     /* rows start at dword alignment only: same 16-byte store, at that alignment; the lane that
-     * holds the last two columns of a width % 4 == 2 frame writes two pixels */
+     * holds the last two columns of a width % 4 == 2 frame writes two pixels (store_two) */
     if (lastmode != 2) {
       if constexpr (ST == 1)
         __builtin_nontemporal_store (px, (u32x4_a4 *) p);
       else
         *(u32x4_a4 *) p = px;
     } else {
-      u32x2 two;
-      two.x = px.x;
-      two.y = px.y;
-      if constexpr (ST == 1)
-        __builtin_nontemporal_store (two, (u32x2_a4 *) p);
-      else
-        *(u32x2_a4 *) p = two;
+      store_two<ST == 1> (p, px);
     }
   }
 }
@@ -250,10 +267,7 @@ __device__ __forceinline__ void store_pixels_hybrid (uint8_t *p, u32x4 px,
   const int need = a7 > 112 ? 256 : 128;        /* the 16 bytes straddle a line boundary: both lines count */
   const bool inside = a7 <= lane16 && lane16 + need - a7 <= len;
   if (lastmode == 2) {
-    u32x2 two;
-    two.x = px.x;
-    two.y = px.y;
-    *(u32x2_a4 *) p = two;
+    store_two<false> (p, px);
   } else if (inside) {
     /* spelled out: the compiler folds an nt and a plain store of the same value under if / else into ONE plain store */
     asm volatile ("global_store_dwordx4 %0, %1, off nt" :: "v" (p), "v" (px) : "memory");
@@ -270,29 +284,124 @@ __device__ __forceinline__ int map_row (int y, int height, int dn_last)
 }
 
 /* ------------------------------------------------------------------------- */
-/* LDS-staged tile kernel                                                      */
+/* what the tile kernels share: shape, tile origin, generic staging, march      */
 /* ------------------------------------------------------------------------- */
 /* WX x WY waves per workgroup; a wave covers 256 px (64 lanes x 4 px) and marches
- * RPW rows.  Tile = (256*WX) x (WY*RPW) px.
- * NEIGH: 0 = DPP wave shift, 1 = __shfl_up/down (ds_bpermute), 2 = LDS reads.   */
+ * RPW rows.  Tile = (256*WX) x (WY*RPW) px, staged with one halo row above and below
+ * in 16-byte chunks, TPR threads per row and RPP rows per pass.  An LDS row starts
+ * with 12 B pad | left halo dword, the tile's bytes follow at MAIN; what lies right
+ * of them (PITCH) is the kernel's own.
+ * The helpers take the kernel arguments as `const KParams &__restrict__`: through a plain reference the compiler
+ * loads the selectors and the geometry again after every row's stores. */
+template <int WX, int WY, int RPW>
+struct TileShape {
+  static constexpr int NTHREADS = 64 * WX * WY;
+  static constexpr int TW = 256 * WX;
+  static constexpr int TR = WY * RPW;
+  static constexpr int NROWS = TR + 2;
+  static constexpr int MAIN = 16;
+  static constexpr int TPR = TW / 16;
+  static constexpr int RPP = NTHREADS / TPR;
+  static constexpr int NPASS = (NROWS + RPP - 1) / RPP;
+  static_assert (RPW % 2 == 0, "row parity is derived from the in-tile row");
+};
+
+/* a tile's frame and its first pixel in it */
+struct Tile { const uint8_t *src; uint8_t *dst; int tile_x, tile_y; };
+
+template <int TW, int TR>
+__device__ __forceinline__ Tile tile_of (const KParams &__restrict__ p, TileId id)
+{
+  const uint32_t frame = fastdiv (id.row, p.map.tiles_y);
+  const int ty = (int) (id.row - frame * p.map.tiles_y.d);
+  Tile t;
+  t.src = frame_src (p, frame);
+  t.dst = frame_dst (p, frame);
+  t.tile_x = (int) id.tx * TW;
+  t.tile_y = ty * TR;
+  return t;
+}
+
+/* Generic geometry: rows tile_y-1 .. tile_y+TR (through map_row) of the tile into LDS in the same 16-byte chunks as the
+ * fast arm, loaded at dword alignment; the chunk that straddles the end of a row (width % 16 != 0) is read dword by
+ * dword up to ROUND_UP_4(width), which the source stride always covers.  Chunks right of the frame are zeros */
+template <class S, int PITCH>
+__device__ __forceinline__ void stage_rows_generic (const KParams &__restrict__ p,
+    const Tile t, int tid, uint8_t *lds)
+{
+  const int c = (tid % S::TPR) * 16;
+  const int rr = tid / S::TPR;
+  const int avail = p.wlimit4 - (t.tile_x + c);         /* readable bytes from this chunk on */
+  u32x4 v[S::NPASS];
+#pragma unroll
+  for (int i = 0; i < S::NPASS; i++) {
+    const int r = i * S::RPP + rr;
+    const int y = t.tile_y - 1 + r;
+    v[i] = (u32x4) (0u);
+    if (r < S::NROWS && y <= p.height && avail > 0) {
+      const uint8_t *g = t.src
+          + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
+          + t.tile_x + c;
+      if (avail >= 16) {
+        v[i] = *(const u32x4_a4 *) g;
+      } else {
+        const uint32_t *q = (const uint32_t *) g;
+        v[i].x = q[0];
+        if (avail > 4) v[i].y = q[1];
+        if (avail > 8) v[i].z = q[2];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < S::NPASS; i++) {
+    const int r = i * S::RPP + rr;
+    if (r < S::NROWS)
+      *(u32x4 *) &lds[r * PITCH + S::MAIN + c] = v[i];
+  }
+}
+
+/* A wave's march down its rows with a 3-row sliding window of (E,O).  lines_of (r): the lines of staged row r, r0 the
+ * one that is up of the wave's first output row; that row is row y0 + r0 of the frame at dst, the lane's columns are
+ * x0..x0+3 (active: inside the frame); store (out, px) writes the four pixels of a row that lies inside the frame */
+template <int RPW, bool INTRIN, class LinesOf, class Store>
+__device__ __forceinline__ void march_rows (const KParams &__restrict__ p, uint8_t *dst,
+    int y0, int r0, int x0, bool active, LinesOf lines_of, Store store)
+{
+  Lines up = lines_of (r0);
+  Lines cur = lines_of (r0 + 1);
+  uint8_t *out = dst + (size_t) (y0 + r0) * p.dst_stride + (size_t) x0 * 4;
+  const int nrows = p.height - (y0 + r0);       /* rows of this wave inside the frame */
+#pragma unroll
+  for (int k = 0; k < RPW; k++) {
+    const Lines dn = lines_of (r0 + k + 2);
+    const int type = (k & 1) ^ p.swap_rows;
+    const u32x4 px = merge_rows<INTRIN> (up, cur, dn, type, p.sel);
+    if (active && k < nrows)
+      store (out, px);
+    out += p.dst_stride;
+    up = cur;
+    cur = dn;
+  }
+}
+
+/* ------------------------------------------------------------------------- */
+/* LDS-staged tile kernel                                                      */
+/* ------------------------------------------------------------------------- */
+/* NEIGH: 0 = DPP wave shift, 1 = __shfl_up/down (ds_bpermute), 2 = LDS reads.   */
 template <int WX, int WY, int RPW, int NEIGH, int ST, bool INTRIN,
     bool GENERIC>
 __global__ void __launch_bounds__ (64 * WX * WY)
 bayer2rgb_lds_kernel (KParams p)
 {
-  constexpr int NTHREADS = 64 * WX * WY;
-  constexpr int TW = 256 * WX;
-  constexpr int TR = WY * RPW;
-  constexpr int NROWS = TR + 2;
+  using S = TileShape<WX, WY, RPW>;
   /* LDS row: 12 B pad | left halo dword | TW bytes | right halo dword | 12 B pad */
-  constexpr int PITCH = TW + 32;
-  constexpr int MAIN = 16;
-  static_assert (RPW % 2 == 0, "row parity is derived from the in-tile row");
+  constexpr int PITCH = S::TW + 32;
+  constexpr int MAIN = S::MAIN;
 
-  __shared__ __attribute__ ((aligned (16))) uint8_t lds[NROWS * PITCH];
+  __shared__ __attribute__ ((aligned (16))) uint8_t lds[S::NROWS * PITCH];
 
-  const TileId tile = block_to_tile (blockIdx.x, p.map);
-  if (!tile.valid)
+  const TileId id = block_to_tile (blockIdx.x, p.map);
+  if (!id.valid)
     return;
   /* start delay: lets the store burst of the workgroup that just
    * retired on this CU drain before this one's loads reach the L2 (input-FIFO-full
@@ -302,12 +411,9 @@ bayer2rgb_lds_kernel (KParams p)
    * stagger, lower occupancy (profiles/r01_sweep_start_delay.log). */
   for (int z = 0; z < p.start_sleep; z++)
     __builtin_amdgcn_s_sleep (1);
-  const uint32_t frame = fastdiv (tile.row, p.map.tiles_y);
-  const int ty = (int) (tile.row - frame * p.map.tiles_y.d);
-  const uint8_t *src = frame_src (p, frame);
-  uint8_t *dst = frame_dst (p, frame);
-  const int tile_x = (int) tile.tx * TW;
-  const int tile_y = ty * TR;
+  const Tile t = tile_of<S::TW, S::TR> (p, id);
+  const int tile_x = t.tile_x;
+  const int tile_y = t.tile_y;
   const int tid = threadIdx.x;
 
   /* ---- stage rows tile_y-1 .. tile_y+TR (through map_row) into LDS ---------- */
@@ -318,16 +424,16 @@ bayer2rgb_lds_kernel (KParams p)
      * WX == 4.  Lanes right of the frame skip their load; what their LDS bytes
      * hold is never used (the last valid lane replaces its right neighbour). */
     static_assert (WX == 4, "one wave stages one 1024-px row");
-    constexpr int RPP = NTHREADS / 64;    /* rows per pass = waves */
-    constexpr int NPASS = (NROWS + RPP - 1) / RPP;
+    constexpr int RPP = S::NTHREADS / 64;    /* rows per pass = waves */
+    constexpr int NPASS = (S::NROWS + RPP - 1) / RPP;
     const int c = (tid & 63) * 16;
     const int rr = tid >> 6;
 #pragma unroll
     for (int i = 0; i < NPASS; i++) {
       const int r = i * RPP + rr;
       const int y = tile_y - 1 + r;
-      if (r < NROWS && y <= p.height && tile_x + c < p.width) {
-        const uint8_t *g = src
+      if (r < S::NROWS && y <= p.height && tile_x + c < p.width) {
+        const uint8_t *g = t.src
             + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
             + tile_x + c;
         __builtin_amdgcn_global_load_lds (
@@ -337,19 +443,16 @@ bayer2rgb_lds_kernel (KParams p)
       }
     }
   } else if constexpr (!GENERIC) {
-    constexpr int TPR = TW / 16;          /* threads per row, 16 B each */
-    constexpr int RPP = NTHREADS / TPR;   /* rows per pass */
-    constexpr int NPASS = (NROWS + RPP - 1) / RPP;
-    const int c = (tid % TPR) * 16;
-    const int rr = tid / TPR;
-    u32x4 v[NPASS];
+    const int c = (tid % S::TPR) * 16;
+    const int rr = tid / S::TPR;
+    u32x4 v[S::NPASS];
 #pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
+    for (int i = 0; i < S::NPASS; i++) {
+      const int r = i * S::RPP + rr;
       const int y = tile_y - 1 + r;
       v[i] = (u32x4) (0u);
-      if (r < NROWS && y <= p.height && tile_x + c < p.width) {
-        const uint8_t *g = src
+      if (r < S::NROWS && y <= p.height && tile_x + c < p.width) {
+        const uint8_t *g = t.src
             + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
             + tile_x + c;
         if constexpr ((ST & 8) != 0)
@@ -359,59 +462,25 @@ bayer2rgb_lds_kernel (KParams p)
       }
     }
 #pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      if (r < NROWS)
+    for (int i = 0; i < S::NPASS; i++) {
+      const int r = i * S::RPP + rr;
+      if (r < S::NROWS)
         *(u32x4 *) &lds[r * PITCH + MAIN + c] = v[i];
     }
   } else {
-    /* generic geometry: the same 16-byte chunks, loaded at dword alignment; the chunk that
-     * straddles the end of a row (width % 16 != 0) is read dword by dword up to ROUND_UP_4(width),
-     * which the source stride always covers */
-    constexpr int TPR = TW / 16;
-    constexpr int RPP = NTHREADS / TPR;
-    constexpr int NPASS = (NROWS + RPP - 1) / RPP;
-    const int c = (tid % TPR) * 16;
-    const int rr = tid / TPR;
-    const int avail = p.wlimit4 - (tile_x + c);         /* readable bytes from this chunk on */
-    u32x4 v[NPASS];
-#pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      const int y = tile_y - 1 + r;
-      v[i] = (u32x4) (0u);
-      if (r < NROWS && y <= p.height && avail > 0) {
-        const uint8_t *g = src
-            + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
-            + tile_x + c;
-        if (avail >= 16) {
-          v[i] = *(const u32x4_a4 *) g;
-        } else {
-          const uint32_t *q = (const uint32_t *) g;
-          v[i].x = q[0];
-          if (avail > 4) v[i].y = q[1];
-          if (avail > 8) v[i].z = q[2];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      if (r < NROWS)
-        *(u32x4 *) &lds[r * PITCH + MAIN + c] = v[i];
-    }
+    stage_rows_generic<S, PITCH> (p, t, tid, lds);
   }
   /* halo dwords: column tile_x-4 and tile_x+TW of every staged row */
-  for (int h = tid; h < 2 * NROWS; h += NTHREADS) {
+  for (int h = tid; h < 2 * S::NROWS; h += S::NTHREADS) {
     const int r = h >> 1;
     const int side = h & 1;
     const int y = tile_y - 1 + r;
-    const int col = side ? tile_x + TW : tile_x - 4;
+    const int col = side ? tile_x + S::TW : tile_x - 4;
     uint32_t v = 0u;
     if (y <= p.height && col >= 0 && col < p.wlimit4)
-      v = *(const uint32_t *) (src
+      v = *(const uint32_t *) (t.src
           + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride + col);
-    *(uint32_t *) &lds[r * PITCH + (side ? MAIN + TW : MAIN - 4)] = v;
+    *(uint32_t *) &lds[r * PITCH + (side ? MAIN + S::TW : MAIN - 4)] = v;
   }
   __syncthreads ();
 
@@ -452,10 +521,12 @@ bayer2rgb_lds_kernel (KParams p)
     return row_lines<INTRIN, GENERIC> (c, cl, cr, first, lastmode);
   };
 
+  /* march_rows, spelled out: called through it the fast arms, which carry the headline number, compile to other code
+   * than the measured one (4 instructions and 4 VGPRs fewer, not timed), so this kernel keeps the loop in its body */
   const int r0 = wy * RPW;      /* LDS row of up(first output row of this wave) */
   Lines up = lines_of (r0);
   Lines cur = lines_of (r0 + 1);
-  uint8_t *out = dst + (size_t) (tile_y + r0) * p.dst_stride + (size_t) x0 * 4;
+  uint8_t *out = t.dst + (size_t) (tile_y + r0) * p.dst_stride + (size_t) x0 * 4;
   const int nrows = p.height - (tile_y + r0);   /* rows of this wave inside the frame */
   /* bytes of a row this wave writes (store policy 5): 1 KiB, less for the wave that holds the end of the row */
   const int wave_left = 4 * (p.width - (tile_x + 256 * wx));
@@ -480,7 +551,7 @@ bayer2rgb_lds_kernel (KParams p)
 /* (E,O) of four columns whose source bytes start R bytes (0 or 2) behind the dword-aligned LDS address qa: the
  * column dword and its x-1 / x+1 neighbour windows all come out of the aligned dwords around it (for R = 2 out of
  * two of them), so no lane exchange and no wave-edge special case is needed.  EDGE: this wave holds the first column
- * of the frame, or its last ones (reference gstbayer2rgb.c:360-363, :372-380) */
+ * of the frame, or its last ones */
 template <int R, bool EDGE>
 __device__ __forceinline__ Lines shifted_lines (const uint8_t *qa, int x, int width)
 {
@@ -497,30 +568,7 @@ __device__ __forceinline__ Lines shifted_lines (const uint8_t *qa, int x, int wi
     c = __builtin_amdgcn_alignbit (d1, d0, 16);
     rsh = __builtin_amdgcn_alignbit (d1, d0, 24);
   }
-  if constexpr (EDGE) {
-    /* O[0] = S[1]: the left neighbour of column 0 is S[1] */
-    const uint32_t lsh_first = (lsh & 0xffffff00u) | ((c >> 8) & 0xffu);
-    lsh = (x == 0) ? lsh_first : lsh;
-    /* E[W-1] = S[W-2], O[W-2] = S[W-3]: the right neighbours of the last two columns are their left ones */
-    const uint32_t t = lsh >> 16;
-    const uint32_t rsh_last = t | (t << 16);
-    rsh = (x + 4 == width) ? rsh_last : rsh;
-    rsh = (x + 2 == width) ? lsh : rsh;
-  }
-  const uint32_t a = avg4<true> (lsh, rsh);
-  Lines r;
-  r.e = bsel (kEvenBytes, c, a);
-  r.o = bsel (kEvenBytes, a, c);
-  return r;
-}
-
-template <int ST>
-__device__ __forceinline__ void store_aligned16 (uint8_t *p, u32x4 px)
-{
-  if constexpr ((ST & 7) == 1)
-    __builtin_nontemporal_store (px, (u32x4 *) p);
-  else
-    *(u32x4 *) p = px;
+  return edge_lines<true> (lsh, c, rsh, EDGE && x == 0, EDGE && x + 4 == width, EDGE && x + 2 == width);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -550,86 +598,48 @@ template <int WX, int WY, int RPW, int ST, int ALIGN>
 __global__ void __launch_bounds__ (64 * WX * WY)
 bayer2rgb_lds_aligned_kernel (KParams p)
 {
-  constexpr int NTHREADS = 64 * WX * WY;
-  constexpr int TW = 256 * WX;
-  constexpr int TR = WY * RPW;
-  constexpr int NROWS = TR + 2;
+  using S = TileShape<WX, WY, RPW>;
   constexpr int SMAX = ALIGN / 4;               /* shifts are 0, 2, .. SMAX - 2 pixels */
   /* LDS row: 12 B pad | left halo dword | TW bytes | RIGHT bytes.  The last lane of the tile at the largest shift
    * reads its right neighbour dword at bytes TW - 4 + (SMAX - 2) + 4 .. + 7 */
   constexpr int RIGHT = (SMAX + 4 + 15) & ~15;
   constexpr int NRIGHT = (SMAX + 4) / 4;        /* dwords staged right of the tile */
-  constexpr int PITCH = 16 + TW + RIGHT;
-  constexpr int MAIN = 16;
-  static_assert (RPW % 2 == 0, "row parity is derived from the in-tile row");
+  constexpr int PITCH = 16 + S::TW + RIGHT;
   static_assert (ALIGN == 64 || ALIGN == 128, "a sector or an L2 line");
 
-  __shared__ __attribute__ ((aligned (16))) uint8_t lds[NROWS * PITCH];
+  __shared__ __attribute__ ((aligned (16))) uint8_t lds[S::NROWS * PITCH];
 
-  const TileId tile = block_to_tile (blockIdx.x, p.map);
-  if (!tile.valid)
+  const TileId id = block_to_tile (blockIdx.x, p.map);
+  if (!id.valid)
     return;
   for (int z = 0; z < p.start_sleep; z++)
     __builtin_amdgcn_s_sleep (1);
-  const uint32_t frame = fastdiv (tile.row, p.map.tiles_y);
-  const int ty = (int) (tile.row - frame * p.map.tiles_y.d);
-  const uint8_t *src = frame_src (p, frame);
-  uint8_t *dst = frame_dst (p, frame);
-  const int tile_x = (int) tile.tx * TW;
-  const int tile_y = ty * TR;
+  const Tile t = tile_of<S::TW, S::TR> (p, id);
+  const int tile_x = t.tile_x;
+  const int tile_y = t.tile_y;
   const int tid = threadIdx.x;
 
   /* ---- stage rows tile_y-1 .. tile_y+TR, columns tile_x-4 .. tile_x+TW+4*NRIGHT-1 ---------- */
   {
-    constexpr int TPR = TW / 16;
-    constexpr int RPP = NTHREADS / TPR;
-    constexpr int NPASS = (NROWS + RPP - 1) / RPP;
-    const int c = (tid % TPR) * 16;
-    const int rr = tid / TPR;
-    const int avail = p.wlimit4 - (tile_x + c);         /* readable bytes from this chunk on */
-    u32x4 v[NPASS];
-#pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      const int y = tile_y - 1 + r;
-      v[i] = (u32x4) (0u);
-      if (r < NROWS && y <= p.height && avail > 0) {
-        const uint8_t *g = src
-            + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
-            + tile_x + c;
-        if (avail >= 16) {
-          v[i] = *(const u32x4_a4 *) g;
-        } else {
-          const uint32_t *q = (const uint32_t *) g;
-          v[i].x = q[0];
-          if (avail > 4) v[i].y = q[1];
-          if (avail > 8) v[i].z = q[2];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      if (r < NROWS)
-        *(u32x4 *) &lds[r * PITCH + MAIN + c] = v[i];
-    }
+    stage_rows_generic<S, PITCH> (p, t, tid, lds);
     /* halo dwords: one left of the tile, NRIGHT right of it */
-    for (int h = tid; h < (1 + NRIGHT) * NROWS; h += NTHREADS) {
+    for (int h = tid; h < (1 + NRIGHT) * S::NROWS; h += S::NTHREADS) {
       const int r = h / (1 + NRIGHT);
       const int k = h - r * (1 + NRIGHT);
       const int y = tile_y - 1 + r;
-      const int off = k == 0 ? -4 : TW + 4 * (k - 1);
+      const int off = k == 0 ? -4 : S::TW + 4 * (k - 1);
       const int col = tile_x + off;
       uint32_t hv = 0u;
       if (y <= p.height && col >= 0 && col < p.wlimit4)
-        hv = *(const uint32_t *) (src
+        hv = *(const uint32_t *) (t.src
             + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride + col);
-      *(uint32_t *) &lds[r * PITCH + MAIN + off] = hv;
+      *(uint32_t *) &lds[r * PITCH + S::MAIN + off] = hv;
     }
   }
   __syncthreads ();
 
-  /* ---- per-wave march -------------------------------------------------------- */
+  /* ---- per-wave rows: no sliding window here.  A row's shift moves the lane -> column map, so the three source
+   * rows of every output row are rebuilt at that row's own shift (by design, see above) and march_rows does not fit */
   const int wave = __builtin_amdgcn_readfirstlane (tid >> 6);
   const int lane = tid & 63;
   const int wx = wave % WX;
@@ -638,8 +648,8 @@ bayer2rgb_lds_aligned_kernel (KParams p)
   const int wave_x0 = tile_x + 256 * wx;
   const int r0 = wy * RPW;
   const int nrows = p.height - (tile_y + r0);   /* rows of this wave inside the frame */
-  const bool head_wave = (tile.tx == 0 && wx == 0);
-  const uint8_t *lrow = &lds[r0 * PITCH + MAIN + xl];
+  const bool head_wave = (id.tx == 0 && wx == 0);
+  const uint8_t *lrow = &lds[r0 * PITCH + S::MAIN + xl];
 
   /* one output row of this wave at shift s: convert, store */
   auto shifted_row = [&](auto rtag, auto etag, const uint8_t *qa, int x, int type, uint8_t *row, int lim) {
@@ -651,17 +661,13 @@ bayer2rgb_lds_aligned_kernel (KParams p)
     const u32x4 px = merge_rows<true> (up, cur, dn, type, p.sel);
     uint8_t *out = row + (size_t) x * 4;
     if constexpr (!EDGE) {
-      store_aligned16<ST> (out, px);
+      store_pixels<ST, false> (out, px, 0);
     } else {
       /* lim: one past the last column this pass may write (the frame width, or the first boundary for the head) */
-      if (x + 4 <= lim) {
+      if (x + 4 <= lim)
         *(u32x4_a4 *) out = px;
-      } else if (x + 2 == lim) {
-        u32x2 two;
-        two.x = px.x;
-        two.y = px.y;
-        *(u32x2_a4 *) out = two;
-      }
+      else if (x + 2 == lim)
+        store_two<false> (out, px);
     }
   };
   using R0 = std::integral_constant<int, 0>;
@@ -671,7 +677,7 @@ bayer2rgb_lds_aligned_kernel (KParams p)
   for (int k = 0; k < RPW; k++) {
     if (k >= nrows)
       break;
-    uint8_t *row = dst + (size_t) (tile_y + r0 + k) * p.dst_stride;
+    uint8_t *row = t.dst + (size_t) (tile_y + r0 + k) * p.dst_stride;
     const int s = (int) (((0u - (uint32_t) (uintptr_t) row) & (uint32_t) (ALIGN - 1)) >> 2);
     const int type = (k & 1) ^ p.swap_rows;
     const uint8_t *qa = lrow + k * PITCH + (s & ~3);
@@ -705,25 +711,19 @@ template <int WX, int WY, int RPW, int ST, bool INTRIN, bool GENERIC>
 __global__ void __launch_bounds__ (64 * WX * WY)
 bayer2rgb_direct_kernel (KParams p)
 {
-  constexpr int TW = 256 * WX;
-  constexpr int TR = WY * RPW;
-  static_assert (RPW % 2 == 0, "row parity is derived from the in-tile row");
+  using S = TileShape<WX, WY, RPW>;
 
-  const TileId tile = block_to_tile (blockIdx.x, p.map);
-  if (!tile.valid)
+  const TileId id = block_to_tile (blockIdx.x, p.map);
+  if (!id.valid)
     return;
-  const uint32_t frame = fastdiv (tile.row, p.map.tiles_y);
-  const int ty = (int) (tile.row - frame * p.map.tiles_y.d);
-  const int tx = (int) tile.tx;
-  const uint8_t *src = frame_src (p, frame);
-  uint8_t *dst = frame_dst (p, frame);
+  const Tile t = tile_of<S::TW, S::TR> (p, id);
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int wx = wave % WX;
   const int wy = wave / WX;
-  const int x0 = tx * TW + 256 * wx + 4 * lane;
-  const int yb = ty * TR + wy * RPW;
+  const int x0 = t.tile_x + 256 * wx + 4 * lane;
+  const int yb = t.tile_y + wy * RPW;
   const bool first = (x0 == 0);
   const int lastmode = (x0 + 4 == p.width) ? 1
       : ((GENERIC && x0 + 2 == p.width) ? 2 : 0);
@@ -740,7 +740,7 @@ bayer2rgb_direct_kernel (KParams p)
     c[r] = 0u;
     e[r] = 0u;
     if (y <= p.height) {
-      const uint8_t *row = src
+      const uint8_t *row = t.src
           + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride;
       if (readable)
         c[r] = *(const uint32_t *) (row + x0);
@@ -755,21 +755,9 @@ bayer2rgb_direct_kernel (KParams p)
     return row_lines<INTRIN, GENERIC> (c[r], cl, cr, first, lastmode);
   };
 
-  Lines up = lines_of (0);
-  Lines cur = lines_of (1);
-  uint8_t *out = dst + (size_t) yb * p.dst_stride + (size_t) x0 * 4;
-  const int nrows = p.height - yb;              /* rows of this wave inside the frame */
-#pragma unroll
-  for (int k = 0; k < RPW; k++) {
-    const Lines dn = lines_of (k + 2);
-    const int type = (k & 1) ^ p.swap_rows;
-    const u32x4 px = merge_rows<INTRIN> (up, cur, dn, type, p.sel);
-    if (active && k < nrows)
-      store_pixels<ST, GENERIC> (out, px, lastmode);
-    out += p.dst_stride;
-    up = cur;
-    cur = dn;
-  }
+  march_rows<RPW, INTRIN> (p, t.dst, yb, 0, x0, active, lines_of, [&](uint8_t *out, u32x4 px) {
+    store_pixels<ST, GENERIC> (out, px, lastmode);
+  });
 }
 
 /* ------------------------------------------------------------------------- */
@@ -788,19 +776,12 @@ template <int WX, int WY, int RPW, int ST>
 __global__ void __launch_bounds__ (64 * WX * WY)
 bayer2rgb_persist_kernel (KParams p)
 {
-  constexpr int NTHREADS = 64 * WX * WY;
-  constexpr int TW = 256 * WX;
-  constexpr int TR = WY * RPW;
-  constexpr int NROWS = TR + 2;
-  constexpr int PITCH = TW + 32;
-  constexpr int MAIN = 16;
-  constexpr int TPR = TW / 16;
-  constexpr int RPP = NTHREADS / TPR;
-  constexpr int NPASS = (NROWS + RPP - 1) / RPP;
-  static_assert (RPW % 2 == 0, "row parity is derived from the in-tile row");
-  static_assert (2 * NROWS <= NTHREADS, "one halo dword per thread");
+  using S = TileShape<WX, WY, RPW>;
+  constexpr int PITCH = S::TW + 32;
+  constexpr int MAIN = S::MAIN;
+  static_assert (2 * S::NROWS <= S::NTHREADS, "one halo dword per thread");
 
-  __shared__ __attribute__ ((aligned (16))) uint8_t lds[2][NROWS * PITCH];
+  __shared__ __attribute__ ((aligned (16))) uint8_t lds[2][S::NROWS * PITCH];
 
   /* this workgroup's tile sequence: first, first+step, ... < end (linear tile ids) */
   const uint32_t ntiles = p.map.tile_rows * p.map.tiles_x.d;
@@ -820,8 +801,8 @@ bayer2rgb_persist_kernel (KParams p)
     return;
 
   const int tid = threadIdx.x;
-  const int c16 = (tid % TPR) * 16;
-  const int rr = tid / TPR;
+  const int c16 = (tid % S::TPR) * 16;
+  const int rr = tid / S::TPR;
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int wx = wave % WX;
@@ -830,38 +811,28 @@ bayer2rgb_persist_kernel (KParams p)
   const int edge_off = (lane == 0) ? -4 : 4;
   const int r0 = wy * RPW;
 
-  struct Tile { const uint8_t *src; uint8_t *dst; int tile_x, tile_y; };
   auto decode = [&](uint32_t tile) -> Tile {
-    const TileId id = linear_to_tile (tile, p.map);
-    const uint32_t frame = fastdiv (id.row, p.map.tiles_y);
-    const int ty = (int) (id.row - frame * p.map.tiles_y.d);
-    const int tx = (int) id.tx;
-    Tile t;
-    t.src = frame_src (p, frame);
-    t.dst = frame_dst (p, frame);
-    t.tile_x = tx * TW;
-    t.tile_y = ty * TR;
-    return t;
+    return tile_of<S::TW, S::TR> (p, linear_to_tile (tile, p.map));
   };
 
-  u32x4 v[NPASS];
+  u32x4 v[S::NPASS];
   uint32_t hv = 0u;
   auto issue = [&](const Tile &t) {
 #pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
+    for (int i = 0; i < S::NPASS; i++) {
+      const int r = i * S::RPP + rr;
       const int y = t.tile_y - 1 + r;
       v[i] = (u32x4) (0u);
-      if (r < NROWS && y <= p.height && t.tile_x + c16 < p.width)
+      if (r < S::NROWS && y <= p.height && t.tile_x + c16 < p.width)
         v[i] = *(const u32x4 *) (t.src
             + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride
             + t.tile_x + c16);
     }
     hv = 0u;
-    if (tid < 2 * NROWS) {
+    if (tid < 2 * S::NROWS) {
       const int r = tid >> 1;
       const int y = t.tile_y - 1 + r;
-      const int col = (tid & 1) ? t.tile_x + TW : t.tile_x - 4;
+      const int col = (tid & 1) ? t.tile_x + S::TW : t.tile_x - 4;
       if (y <= p.height && col >= 0 && col < p.wlimit4)
         hv = *(const uint32_t *) (t.src
             + (size_t) map_row (y, p.height, p.dn_last) * p.src_stride + col);
@@ -869,13 +840,13 @@ bayer2rgb_persist_kernel (KParams p)
   };
   auto commit = [&](uint8_t *buf) {
 #pragma unroll
-    for (int i = 0; i < NPASS; i++) {
-      const int r = i * RPP + rr;
-      if (r < NROWS)
+    for (int i = 0; i < S::NPASS; i++) {
+      const int r = i * S::RPP + rr;
+      if (r < S::NROWS)
         *(u32x4 *) &buf[r * PITCH + MAIN + c16] = v[i];
     }
-    if (tid < 2 * NROWS)
-      *(uint32_t *) &buf[(tid >> 1) * PITCH + ((tid & 1) ? MAIN + TW : MAIN - 4)]
+    if (tid < 2 * S::NROWS)
+      *(uint32_t *) &buf[(tid >> 1) * PITCH + ((tid & 1) ? MAIN + S::TW : MAIN - 4)]
           = hv;
   };
   auto compute = [&](const Tile &t, const uint8_t *buf) {
@@ -891,22 +862,9 @@ bayer2rgb_persist_kernel (KParams p)
       return row_lines<true, false> (c, from_lane_below (edge, c),
           from_lane_above (edge, c), first_lane, lastmode);
     };
-    Lines up = lines_of (r0);
-    Lines cur = lines_of (r0 + 1);
-    uint8_t *out = t.dst + (size_t) (t.tile_y + r0) * p.dst_stride
-        + (size_t) x0 * 4;
-    const int nrows = p.height - (t.tile_y + r0);
-#pragma unroll
-    for (int k = 0; k < RPW; k++) {
-      const Lines dn = lines_of (r0 + k + 2);
-      const int type = (k & 1) ^ p.swap_rows;
-      const u32x4 px = merge_rows<true> (up, cur, dn, type, p.sel);
-      if (active && k < nrows)
-        store_pixels<ST, false> (out, px, lastmode);
-      out += p.dst_stride;
-      up = cur;
-      cur = dn;
-    }
+    march_rows<RPW, true> (p, t.dst, t.tile_y, r0, x0, active, lines_of, [&](uint8_t *out, u32x4 px) {
+      store_pixels<ST, false> (out, px, lastmode);
+    });
   };
 
   Tile cur_tile = decode (first);
@@ -940,8 +898,10 @@ bayer2rgb_persist_kernel (KParams p)
 /* default block order per shape (measured on a dozen boxes, DESIGN.md "XCD map"):
  * 1024-px tiles -> band 1 (an XCD takes one full-width tile row at a time), the
  * only plan at 80-81.5 % of peak on EVERY box; narrower tiles -> identity */
+/* tile width, tile height, threads */
+#define VARIANT_SHAPE(WX, WY, RPW) 256 * (WX), (WY) * (RPW), 64 * (WX) * (WY)
 #define LDS_VARIANT(name, WX, WY, RPW, NEIGH, ST, INTRIN)                      \
-  { name, 256 * (WX), (WY) * (RPW), 64 * (WX) * (WY), (WX) == 4 ? 1 : 0, 0,    \
+  { name, VARIANT_SHAPE (WX, WY, RPW), (WX) == 4 ? 1 : 0, 0,                   \
     bayer2rgb_lds_kernel<WX, WY, RPW, NEIGH, ST, INTRIN, false>,               \
     bayer2rgb_lds_kernel<WX, WY, RPW, NEIGH, ST, INTRIN, true>, nullptr, nullptr }
 /* production shapes and their plain-store twins: + the sector-aligned arms for generic geometries (the 64-byte
@@ -952,18 +912,18 @@ bayer2rgb_persist_kernel (KParams p)
 #define ALIGNED64_ARM(WX, WY, RPW, ST) nullptr
 #endif
 #define LDS_VARIANT_AL(name, WX, WY, RPW, ST)                                  \
-  { name, 256 * (WX), (WY) * (RPW), 64 * (WX) * (WY), (WX) == 4 ? 1 : 0, 0,    \
+  { name, VARIANT_SHAPE (WX, WY, RPW), (WX) == 4 ? 1 : 0, 0,                   \
     bayer2rgb_lds_kernel<WX, WY, RPW, 0, ST, true, false>,                     \
     bayer2rgb_lds_kernel<WX, WY, RPW, 0, ST, true, true>,                      \
     ALIGNED64_ARM (WX, WY, RPW, ST),                                           \
     bayer2rgb_lds_aligned_kernel<WX, WY, RPW, ST, 128> }
 #ifdef MIBAYER_LAB
 #define PERSIST_VARIANT(name, WX, WY, RPW, ST)                                 \
-  { name, 256 * (WX), (WY) * (RPW), 64 * (WX) * (WY), -1, 1,                   \
+  { name, VARIANT_SHAPE (WX, WY, RPW), -1, 1,                                  \
     bayer2rgb_persist_kernel<WX, WY, RPW, ST>,                                 \
     bayer2rgb_lds_kernel<WX, WY, RPW, 0, ST, true, true>, nullptr, nullptr }
 #define DIRECT_VARIANT(name, WX, WY, RPW, ST, INTRIN)                          \
-  { name, 256 * (WX), (WY) * (RPW), 64 * (WX) * (WY), -1, 0,                   \
+  { name, VARIANT_SHAPE (WX, WY, RPW), -1, 0,                                  \
     bayer2rgb_direct_kernel<WX, WY, RPW, ST, INTRIN, false>,                   \
     bayer2rgb_direct_kernel<WX, WY, RPW, ST, INTRIN, true>, nullptr, nullptr }
 #endif
@@ -991,7 +951,7 @@ static const Variant kVariants[] = {
   LDS_VARIANT ("lds_2x4_r4_dpp_hy", 2, 4, 4, 0, 5, true),
   LDS_VARIANT ("lds_1x8_r4_dpp_hy", 1, 8, 4, 0, 5, true),
 #ifdef MIBAYER_LAB
-  /* 10.. : tuning / verification arms of the lab build (`make lab`), all bit-exact (tests/test_gpu_parity.py);
+  /* 10.. : tuning / verification arms of the lab build (`make lab`), all bit-exact (tests/test_gpu_lab_arms.py);
    * what each of them measured is in profiles/r01_sweep_*.log */
   LDS_VARIANT ("lds_1x8_r4_dpp_sc1", 1, 8, 4, 0, 2, true),
   LDS_VARIANT ("lds_1x8_r4_shfl_nt", 1, 8, 4, 1, 1, true),
