@@ -41,6 +41,9 @@ FORMATS = {
 FORMATS16 = {"ARGB64": (1, 2, 3), "RGBA64": (0, 1, 2), "BGRA64": (2, 1, 0), "ABGR64": (3, 2, 1)}
 # packed 24-bit output (MIBAYER_FLAG_DST_24BIT): byte offsets inside the 3-byte pixel -- RGBx / BGRx without byte 3
 FORMATS24 = {"RGB": (0, 1, 2), "BGR": (2, 1, 0)}
+# planar 8-bit output (MIBAYER_FLAG_DST_PLANAR): the PLANE INDICES of R, G, B; the other three permutations of (0, 1, 2)
+# go in as a tuple with flags=FLAG_DST_PLANAR
+FORMATS_PLANAR = {"RGBP": (0, 1, 2), "BGRP": (2, 1, 0), "GBR": (2, 0, 1)}
 SRC_BITS = (10, 12, 14, 16)     # MIBAYER_FLAG_SRC_BITS(n) values besides 0 (the 8-bit mosaic)
 
 PLAN_DEFAULT, PLAN_MEASURED, PLAN_CACHED, PLAN_SET = 0, 1, 2, 3
@@ -87,6 +90,7 @@ FLAG_SRC_BIG_ENDIAN = 1 << 13
 FLAG_DST_16BIT = 1 << 14
 FLAG_DST_BIG_ENDIAN = 1 << 15
 FLAG_DST_24BIT = 1 << 21        # 3-byte pixels, RGB / BGR; dst_stride defaults to ROUND_UP_4(3 * width)
+FLAG_DST_PLANAR = 1 << 22       # three planes of dst_stride x height bytes; dst_stride defaults to ROUND_UP_4(width)
 FLAG_MHC = 1 << 16              # Malvar-He-Cutler demosaic instead of the reference's bilinear one
 METHODS = {"bilinear": 0, "mhc": FLAG_MHC}      # the `method` keyword of make_cfg / Context / Pool
 FLAG_COLOUR = 1 << 19           # fused colour stage: black level, Q12 matrix, tone curve (struct mibayer_colour)
@@ -370,8 +374,8 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
              inflight=0, variant=0, flags=0, bits=0, src_big_endian=False, out16=False, dst_big_endian=False,
              method="bilinear", colour=None):
     """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
-    name implies out16, a FORMATS24 name ("RGB", "BGR") FLAG_DST_24BIT.  method: "bilinear" (the reference's,
-    bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
+    name implies out16, a FORMATS24 name ("RGB", "BGR") FLAG_DST_24BIT, a FORMATS_PLANAR name FLAG_DST_PLANAR.
+    method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
     colour: None / False = no colour stage; True or a Colour = FLAG_COLOUR (Context / Pool apply the Colour)"""
     if colour is not None and colour is not False:
         flags |= FLAG_COLOUR
@@ -384,12 +388,24 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
     elif isinstance(fmt, str) and fmt in FORMATS24:
         flags |= FLAG_DST_24BIT
         r, g, b = FORMATS24[fmt]
+    elif isinstance(fmt, str) and fmt in FORMATS_PLANAR:
+        flags |= FLAG_DST_PLANAR
+        r, g, b = FORMATS_PLANAR[fmt]
     else:
         r, g, b = FORMATS[fmt] if isinstance(fmt, str) else fmt
     flags |= deep_flags(bits, src_big_endian, out16, dst_big_endian)
     pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
     return Cfg(ctypes.sizeof(Cfg), width, height, src_stride, dst_stride, pat, r, g, b,
                device, inflight, variant, flags)
+
+
+def planes(frame, width, height, dst_stride=0):
+    """A converted planar frame (MIBAYER_FLAG_DST_PLANAR, 3 * dst_stride * height bytes) viewed as (3, height, width):
+    plane k, row y, the first `width` bytes of the stride.  frame: a numpy uint8 array (the host path's), or a torch
+    uint8 tensor -- over device memory the context converted into through its data_ptr(), as bench.py passes tensors --
+    and the result is of the same kind.  A view of the same memory: nothing is copied or computed."""
+    stride = dst_stride or (width + 3) & ~3
+    return frame.reshape(3, height, stride)[:, :, :width]
 
 
 class Pool:
@@ -517,9 +533,11 @@ class Context:
         self.width, self.height = out.width, out.height
         self.src_stride, self.dst_stride = out.src_stride, out.dst_stride
         self.src_bytes = out.src_stride * out.height
-        self.dst_bytes = out.dst_stride * out.height
+        self.planar = bool(out.flags & FLAG_DST_PLANAR)
+        self.dst_rows = (3 if self.planar else 1) * out.height  # rows of dst_stride bytes in a frame (stacked planes)
+        self.dst_bytes = out.dst_stride * self.dst_rows
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
-        self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT | FLAG_DST_24BIT))
+        self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT | FLAG_DST_24BIT | FLAG_DST_PLANAR))
         self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
         self.colour = bool(out.flags & FLAG_COLOUR)
         self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
@@ -596,11 +614,11 @@ class Context:
 
     # -- host path --------------------------------------------------------------------------
     def process_host(self, src, dst=None):
-        """src: uint8 array of src_stride*height bytes -> (height, dst_stride) uint8."""
+        """src: uint8 array of src_stride*height bytes -> (height, dst_stride) uint8; planar: (3*height, dst_stride)."""
         src = self._src_bytes(src)
         assert src.size == self.src_bytes, (src.size, self.src_bytes)
         if dst is None:
-            dst = np.full((self.height, self.dst_stride), 0xA5, np.uint8)
+            dst = np.full((self.dst_rows, self.dst_stride), 0xA5, np.uint8)
         assert dst.size == self.dst_bytes and dst.flags.c_contiguous
         _check(lib().mibayer_process_host(self._h, _ptr(src), _ptr(dst)), "mibayer_process_host")
         return dst
@@ -778,7 +796,7 @@ class Context:
 
     # -- convenience for tests ---------------------------------------------------------------
     def process_batch_via_device(self, frames):
-        """frames: (N, height, src_stride) uint8 on the host -> (N, height, dst_stride) uint8,
+        """frames: (N, height, src_stride) uint8 on the host -> (N, height, dst_stride) uint8 (planar: N, 3*height, .),
         through ONE device-resident batch launch (mibayer_process_device)."""
         if self.deep and frames.dtype != np.uint8:
             frames = np.ascontiguousarray(frames).view(np.uint8).reshape(frames.shape[0], -1)
@@ -795,4 +813,9 @@ class Context:
         finally:
             self.device_free(d_src)
             self.device_free(d_dst)
-        return out.reshape(n, self.height, self.dst_stride)
+        return out.reshape(n, self.dst_rows, self.dst_stride)
+
+    def planes(self, frame):
+        """planes() of a frame this context converted"""
+        assert self.planar
+        return planes(frame, self.width, self.height, self.dst_stride)

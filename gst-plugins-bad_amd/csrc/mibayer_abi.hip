@@ -822,6 +822,11 @@ static void make_deep_plan (mibayer_ctx *c)
   q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
   q.out_shift = c->kind.out16 ? 16 - depth : depth - 8;
   q.px3 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
+  if (f.flags & MIBAYER_FLAG_DST_PLANAR) {
+    /* the offsets are plane indices; the bilinear kernel's R' / B' are B / R for rggb / gbrg (plan_selectors) */
+    const bool swap = !(c->kind.mhc || c->colour) && (f.pattern == MIBAYER_RGGB || f.pattern == MIBAYER_GBRG);
+    q.planar = 0x100 | (swap ? f.b_off : f.r_off) | f.g_off << 2 | (swap ? f.r_off : f.b_off) << 4;
+  }
   if (c->kind.mhc || c->colour)
     make_cgd_selectors (c, depth);
   for (int k = 0; k < 4; k++)
@@ -1213,7 +1218,7 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   if (f.pattern < MIBAYER_BGGR || f.pattern > MIBAYER_RGGB)
     return MIBAYER_ERR_ARG;
   constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
-      | MIBAYER_FLAG_DST_BIG_ENDIAN | MIBAYER_FLAG_DST_24BIT;
+      | MIBAYER_FLAG_DST_BIG_ENDIAN | MIBAYER_FLAG_DST_24BIT | MIBAYER_FLAG_DST_PLANAR;
   if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags
           | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
@@ -1230,6 +1235,8 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     return MIBAYER_ERR_ARG;
   if ((f.flags & MIBAYER_FLAG_DST_24BIT) && (f.flags & MIBAYER_FLAG_DST_16BIT))
     return MIBAYER_ERR_ARG;                     /* 3-byte pixels have 8-bit channels */
+  if ((f.flags & MIBAYER_FLAG_DST_PLANAR) && (f.flags & (MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT)))
+    return MIBAYER_ERR_ARG;                     /* planes of 8-bit samples, and planes are not pixels */
   if ((f.flags & MIBAYER_FLAG_HIPGRAPH_CHAIN) && !(f.flags & MIBAYER_FLAG_HIPGRAPH))
     return MIBAYER_ERR_ARG;
   if (f.flags & MIBAYER_FLAG_RGB2BAYER) {
@@ -1272,19 +1279,29 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   const int src_row = src_bits ? 2 * f.width : (f.width + 3) & ~3;
   const bool dst16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
   const bool dst24 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
-  if ((src_bits || dst16 || dst24) && f.width > (1 << 26))
+  const bool planar = (f.flags & MIBAYER_FLAG_DST_PLANAR) != 0;
+  if ((src_bits || dst16 || dst24 || planar) && f.width > (1 << 26))
     return MIBAYER_ERR_GEOMETRY;
-  const int dst_px = dst16 ? 8 : dst24 ? 3 : 4;
+  const int dst_px = dst16 ? 8 : dst24 ? 3 : planar ? 1 : 4;    /* bytes of a pixel in a row (of a plane) */
   if (f.src_stride == 0)
     f.src_stride = src_row;             /* GST_ROUND_UP_4, gstbayer2rgb.c:477 */
-  if (f.dst_stride == 0)                /* gstbayer2rgb.c:344; 3-byte pixels: GStreamer's RGB stride, ROUND_UP_4 (3 w) */
+  if (f.dst_stride == 0)                /* gstbayer2rgb.c:344; 3-byte pixels: GStreamer's RGB stride, ROUND_UP_4 (3 w);
+                                           planes: ROUND_UP_4 (w) */
     f.dst_stride = (dst_px * f.width + 3) & ~3;
   if (f.src_stride < src_row || (f.src_stride & 3))
     return MIBAYER_ERR_GEOMETRY;
   if (f.dst_stride < dst_px * f.width || (f.dst_stride & (dst16 ? 7 : 3)))
     return MIBAYER_ERR_GEOMETRY;
   /* 3-byte pixels: RGB or BGR -- the bytes of RGBx / BGRx without the fourth, so the selectors are those layouts' */
-  if (dst24 ? !(f.g_off == 1 && ((f.r_off == 0 && f.b_off == 2) || (f.r_off == 2 && f.b_off == 0)))
+  if (planar) {
+    /* planes: the offsets are the plane indices of R, G, B, any permutation of (0, 1, 2); a frame is three planes of
+     * dst_stride x height bytes, and its size has to fit the size_t that carries it */
+    if ((unsigned) f.r_off > 2u || (unsigned) f.g_off > 2u || (unsigned) f.b_off > 2u || f.r_off == f.g_off
+        || f.g_off == f.b_off || f.r_off == f.b_off)
+      return MIBAYER_ERR_LAYOUT;
+    if (3ull * (unsigned long long) f.dst_stride * (unsigned long long) f.height > (unsigned long long) SIZE_MAX)
+      return MIBAYER_ERR_GEOMETRY;
+  } else if (dst24 ? !(f.g_off == 1 && ((f.r_off == 0 && f.b_off == 2) || (f.r_off == 2 && f.b_off == 0)))
       : !layout_known (f.r_off, f.g_off, f.b_off))
     return MIBAYER_ERR_LAYOUT;
   if (f.inflight == 0)
@@ -1412,7 +1429,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->cfg = f;
   c->device = dev;
   c->src_bytes = (size_t) f.src_stride * f.height;
-  c->dst_bytes = (size_t) f.dst_stride * f.height;
+  c->dst_bytes = (size_t) f.dst_stride * f.height * ((f.flags & MIBAYER_FLAG_DST_PLANAR) ? 3 : 1);
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
   c->kind.mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
   c->colour = (f.flags & MIBAYER_FLAG_COLOUR) != 0;
@@ -1421,7 +1438,8 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
     (void) colour_stage_from (&c->colour_user, &c->colour_stage);
   }
   c->deep = c->kind.mhc || c->colour
-      || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT)) != 0;
+      || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT
+              | MIBAYER_FLAG_DST_PLANAR)) != 0;
   {
     int cus = 0;
     if (hipDeviceGetAttribute (&cus, hipDeviceAttributeMultiprocessorCount,
@@ -1754,7 +1772,7 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   if (rc != MIBAYER_OK)
     return rc;
   if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT
-          | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
+          | MIBAYER_FLAG_DST_PLANAR | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -2141,6 +2159,12 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
   return MIBAYER_OK;
 }
 
+/* planes of a destination frame, one under the other at dst_stride: 3 with MIBAYER_FLAG_DST_PLANAR */
+static int dst_planes (const mibayer_ctx *c)
+{
+  return (c->cfg.flags & MIBAYER_FLAG_DST_PLANAR) ? 3 : 1;
+}
+
 /* Host path, one frame cut into horizontal bands: band b's kernel needs source
  * rows y0-1 .. y1 (one halo row above and below; MHC: y0-2 .. y1+1), so upload chunk b carries the
  * band's rows plus the halo rows below it, and the chunks run down the frame in one
@@ -2220,16 +2244,19 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     }
     HIP_TRY (hipEventRecord (s.ev_band_kernel[b], c->s_compute));
     HIP_TRY (hipStreamWaitEvent (c->s_d2h, s.ev_band_kernel[b], 0));
-    const size_t doff = (size_t) y0 * f.dst_stride;
-    if ((size_t) f.dst_stride == row_bytes) {
-      HIP_TRY (hipMemcpyAsync (dst + doff, s.d_dst + doff,
-              (size_t) (y1 - y0) * f.dst_stride, hipMemcpyDeviceToHost,
-              c->s_d2h));
-    } else {
-      /* padded destination rows: only the written bytes of each row */
-      HIP_TRY (hipMemcpy2DAsync (dst + doff, (size_t) f.dst_stride,
-              s.d_dst + doff, (size_t) f.dst_stride, row_bytes,
-              (size_t) (y1 - y0), hipMemcpyDeviceToHost, c->s_d2h));
+    /* planar output: the band is rows [y0, y1) of each of the three planes */
+    for (int k = 0; k < dst_planes (c); k++) {
+      const size_t doff = ((size_t) k * f.height + y0) * f.dst_stride;
+      if ((size_t) f.dst_stride == row_bytes) {
+        HIP_TRY (hipMemcpyAsync (dst + doff, s.d_dst + doff,
+                (size_t) (y1 - y0) * f.dst_stride, hipMemcpyDeviceToHost,
+                c->s_d2h));
+      } else {
+        /* padded destination rows: only the written bytes of each row */
+        HIP_TRY (hipMemcpy2DAsync (dst + doff, (size_t) f.dst_stride,
+                s.d_dst + doff, (size_t) f.dst_stride, row_bytes,
+                (size_t) (y1 - y0), hipMemcpyDeviceToHost, c->s_d2h));
+      }
     }
   }
   const int src_rc = slot_download_stats (c, s);
@@ -2344,9 +2371,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
             c->s_d2h));
   } else {
     /* padded destination rows: only the written bytes of each row may be
-     * touched (the reference never writes the padding either) */
+     * touched (the reference never writes the padding either); planes lie one under the other */
     HIP_TRY (hipMemcpy2DAsync (dst, (size_t) c->cfg.dst_stride, s.d_dst,
-            (size_t) c->cfg.dst_stride, row_bytes, (size_t) c->cfg.height,
+            (size_t) c->cfg.dst_stride, row_bytes, (size_t) c->cfg.height * dst_planes (c),
             hipMemcpyDeviceToHost, c->s_d2h));
   }
   const int stats_rc = slot_download_stats (c, s);
@@ -2359,7 +2386,8 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 static size_t written_row_bytes (const mibayer_ctx *c)
 {
   return c->inverse ? (size_t) ((c->cfg.width + 3) & ~3)
-      : (size_t) (c->kind.out16 ? 8 : (c->cfg.flags & MIBAYER_FLAG_DST_24BIT) ? 3 : 4) * c->cfg.width;
+      : (size_t) (c->kind.out16 ? 8 : (c->cfg.flags & MIBAYER_FLAG_DST_24BIT) ? 3 : dst_planes (c) == 3 ? 1 : 4)
+      * c->cfg.width;
 }
 
 static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
@@ -3682,9 +3710,10 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
     size_t src_frame_bytes, uint32_t first_frame, int nframes, uint32_t seed,
     void *hip_stream)
 {
-  /* the generator writes 8-bit mosaics: an MHC, colour or 24-bit context of one takes it, no other deep context does */
+  /* the generator writes 8-bit mosaics: an MHC, colour, 24-bit or planar context of one takes it, no other deep context
+   * does */
   if (!c || !d_src || nframes < 0 || c->inverse
-      || (c->deep && !((c->kind.mhc || c->colour || c->deep_args.px3) && c->kind.in8)))
+      || (c->deep && !((c->kind.mhc || c->colour || c->deep_args.px3 || c->deep_args.planar) && c->kind.in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

@@ -259,6 +259,13 @@ struct DeepParams {
                                    {x = [C, G], y = [D, 0]} at output depth; 4-byte output uses [.][0] only */
   int px3;                      /* 8-bit channels only: 3-byte pixels (MIBAYER_FLAG_DST_24BIT), the selectors those of
                                    RGBx / BGRx and byte 3 dropped at the store (store_strip8) */
+  int planar;                   /* 8-bit channels only, 0 or 0x100 | p0 | p1 << 2 | p2 << 4: three planes instead of
+                                   pixels (MIBAYER_FLAG_DST_PLANAR, store_planes8), plane k = rows [k * height,
+                                   (k + 1) * height) of dst_stride bytes (the plane pitch is height * dst_stride).
+                                   p0, p1, p2 = the plane index of the kernel's three operands: R, G, B (MHC, colour
+                                   stage); the bilinear kernel's R', G, B' -- R' / B' swapped for rggb / gbrg like its
+                                   selectors, which are not used.  One field: the colour kernel has no scalar register
+                                   to spare */
   /* filled by launch_strip */
   int groups;                   /* 4-pixel groups per row = ceil (width / 4) */
   FastDiv div_tiles_x;          /* 256-pixel strips per row */
@@ -292,7 +299,8 @@ struct ColourParams {
 struct StripKind { bool mhc, in8, out16; };
 /* One launch of a strip kernel over chunks [chunk0, chunk0 + nchunks) of the batch (nchunks < 0: all of p.nlist frames,
  * or of `nframes`).  stage = NULL: bayer2rgb_deep_kernel / bayer2rgb_mhc_kernel of the kind; bilinear 8-bit mosaic to
- * 4-byte pixels is refused (the production kernels serve it; to 3-byte pixels, p.px3, it is the deep kernel's).
+ * 4-byte pixels is refused (the production kernels serve it; to 3-byte pixels, p.px3, or planes, p.planar, it is the
+ * deep kernel's).
  * Otherwise bayer2rgb_colour_kernel with that stage: one
  * kernel for both demosaic methods and all four input / output combinations (uniform run-time branches) */
 hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,

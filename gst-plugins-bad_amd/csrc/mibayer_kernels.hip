@@ -1581,6 +1581,66 @@ __device__ __forceinline__ void store_strip8 (uint8_t *out, int g, bool store, b
   }
 }
 
+/* byte K of each of x[0..3] as one dword: the plane dword of a channel whose four values sit in byte K */
+template <int K>
+__device__ __forceinline__ uint32_t gather_byte (const uint32_t (&x)[4])
+{
+  constexpr uint32_t kSel = 0x0c0c0000u | ((4u + K) << 8) | K;
+  return __builtin_amdgcn_perm (x[1], x[0], kSel) | (__builtin_amdgcn_perm (x[3], x[2], kSel) << 16);
+}
+
+/* row j of plane k of the frame at dst, as a scalar: read back through v_readfirstlane so that the lane's 32-bit column
+ * offset stays apart from it (a store of scalar base + 32-bit lane offset) instead of a 64-bit address per lane and
+ * plane.  The address is rebuilt from integers, so it is typed as global memory again (a plain pointer would make the
+ * stores flat_store_*) */
+typedef __attribute__ ((address_space (1))) uint8_t global_u8;
+typedef __attribute__ ((address_space (1))) uint16_t global_u16;
+typedef __attribute__ ((address_space (1))) uint32_t global_u32;
+__device__ __forceinline__ global_u8 *plane_row (const DeepParams &p, uint8_t *out, int k)
+{
+  const uint64_t q = (uint64_t) out + (uint64_t) (uint32_t) (k * p.height) * (uint64_t) (uint32_t) p.dst_stride;
+  const uint32_t lo = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (uint32_t) q);
+  const uint32_t hi = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (uint32_t) (q >> 32));
+  return (global_u8 *) (((uint64_t) hi << 32) | lo);
+}
+
+/* DeepParams::planar as the row loops read it, once per row: the empty asm keeps the test and the plane bases out of
+ * the loops' invariants, so p.planar is the only scalar that lives across a row for them, and the bases cost a few
+ * scalar instructions per row (the colour kernel has no scalar register to spare: hoisted, they would be spilled) */
+__device__ __forceinline__ int planar_of (const DeepParams &p)
+{
+  int planes = p.planar;
+  asm volatile ("" : "+s" (planes));
+  return planes;
+}
+
+/* planes of 8-bit samples (planes = planar_of (p) != 0, wave-uniform; MIBAYER_FLAG_DST_PLANAR): out = the row in plane
+ * 0; a, b, c = the lane's four samples of operands ka, 1 and kc (DeepParams::planar has their planes), one dword each.
+ * Plane k is rows [k * height, (k + 1) * height) of the frame, so a row's base is scalar and the lane adds 4 g: one
+ * streaming dword store per plane, 256 contiguous bytes per wave and plane; the two samples of a width % 4 == 2 tail
+ * (!full) as a 16-bit store and not a byte more (the next row, or the next plane, may start there); store = the group
+ * is inside the row */
+__device__ __forceinline__ void store_planes8 (const DeepParams &p, int planes, uint8_t *out, int g, bool store,
+    bool full, int ka, int kc, uint32_t a, uint32_t b, uint32_t c)
+{
+  if (store) {
+    uint32_t x = 4u * (uint32_t) g;
+    asm volatile ("" : "+v" (x));       /* per row, like the bases: no 64-bit lane offset kept across the rows */
+    global_u8 *qa = plane_row (p, out, (planes >> (2 * ka)) & 3) + x;
+    global_u8 *qb = plane_row (p, out, (planes >> 2) & 3) + x;
+    global_u8 *qc = plane_row (p, out, (planes >> (2 * kc)) & 3) + x;
+    if (full) {
+      __builtin_nontemporal_store (a, (global_u32 *) qa);
+      __builtin_nontemporal_store (b, (global_u32 *) qb);
+      __builtin_nontemporal_store (c, (global_u32 *) qc);
+    } else {
+      __builtin_nontemporal_store ((uint16_t) a, (global_u16 *) qa);
+      __builtin_nontemporal_store ((uint16_t) b, (global_u16 *) qb);
+      __builtin_nontemporal_store ((uint16_t) c, (global_u16 *) qc);
+    }
+  }
+}
+
 /* 8-byte pixels of group g: v0 = pixels 0,1 and v1 = pixels 2,3.  A lane holds 32 contiguous bytes, so two stores
  * straight from its registers would each fill every other 16 bytes of the wave's 2 KiB.  The four lanes of a quad swap
  * pieces instead (DPP quad_perm): the first store writes the quad's first 64 bytes, the second its last 64, and
@@ -1689,12 +1749,17 @@ bayer2rgb_deep_kernel (DeepParams p)
       const uint32_t m_lo = rb_lo | (b_lo << 8);
       const uint32_t m_hi = rb_hi | (b_hi << 8);
       const uint32_t gw = __builtin_amdgcn_perm (g_hi, g_lo, 0x06040200u);
-      u32x4 v;
-      v.x = __builtin_amdgcn_perm (m_lo, gw, p.sel[0]);
-      v.y = __builtin_amdgcn_perm (m_lo, gw, p.sel[1]);
-      v.z = __builtin_amdgcn_perm (m_hi, gw, p.sel[2]);
-      v.w = __builtin_amdgcn_perm (m_hi, gw, p.sel[3]);
-      store_strip8 (out, g, store, full, p.px3 != 0, v);
+      if (const int planes = planar_of (p)) {   /* gw is the green plane's dword; R', B' are M's even, odd bytes */
+        store_planes8 (p, planes, out, g, store, full, 0, 2, __builtin_amdgcn_perm (m_hi, m_lo, 0x06040200u), gw,
+            __builtin_amdgcn_perm (m_hi, m_lo, 0x07050301u));
+      } else {
+        u32x4 v;
+        v.x = __builtin_amdgcn_perm (m_lo, gw, p.sel[0]);
+        v.y = __builtin_amdgcn_perm (m_lo, gw, p.sel[1]);
+        v.z = __builtin_amdgcn_perm (m_hi, gw, p.sel[2]);
+        v.w = __builtin_amdgcn_perm (m_hi, gw, p.sel[3]);
+        store_strip8 (out, g, store, full, p.px3 != 0, v);
+      }
     }
     up = cur;
     cur = dn;
@@ -1898,6 +1963,9 @@ bayer2rgb_mhc_kernel (DeepParams p)
       u32x4 v0, v1;
       emit_cgd<true> (x, y, s0, s1, v0, v1);
       store_strip16 (p, out, g, lane, v0, v1);
+    } else if (const int planes = planar_of (p)) {      /* C, G, D: bytes 0, 2 of x, 0 of y; C is R in a red row */
+      store_planes8 (p, planes, out, g, store, full, rk ? 2 : 0, rk ? 0 : 2, gather_byte<0> (x), gather_byte<2> (x),
+          gather_byte<0> (y));
     } else {
       const uint32_t s0 = p.sel_cgd[rk][0];
       u32x4 v, unused;
@@ -2121,6 +2189,8 @@ bayer2rgb_colour_kernel (ColourParams cp)
       u32x4 v0, v1;
       emit_cgd<true> (x, y, s0, s1, v0, v1);
       store_strip16 (p, out, g, lane, v0, v1);
+    } else if (const int planes = planar_of (p)) {
+      store_planes8 (p, planes, out, g, store, full, 0, 2, gather_byte<0> (x), gather_byte<2> (x), gather_byte<0> (y));
     } else {
       u32x4 vv, unused;
       emit_cgd<false> (x, y, s0, s0, vv, unused);
@@ -2168,7 +2238,8 @@ static hipError_t deep_grid (DeepParams &q, int nframes, long long chunk0, long 
 }
 
 typedef void (*StripFn) (DeepParams);
-/* [mhc][in8][out16]; bilinear 8 -> 8 is the production (LDS) kernels' unless the pixels are 3 bytes (px3) */
+/* [mhc][in8][out16]; bilinear 8 -> 8 is the production (LDS) kernels' unless the pixels are 3 bytes (px3) or the output
+ * is planes (planar) */
 static const StripFn kStripKernels[2][2][2] = {
   { { bayer2rgb_deep_kernel<false, false>, bayer2rgb_deep_kernel<false, true> },
     { bayer2rgb_deep_kernel<true, false>, bayer2rgb_deep_kernel<true, true> } },
@@ -2180,9 +2251,10 @@ hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage 
     long long chunk0, long long nchunks)
 {
   const StripFn fn = kStripKernels[kind.mhc][kind.in8][kind.out16];
-  if (p.width < 4 || p.height < 3 || (p.width & 1) || (p.px3 && kind.out16))
+  if (p.width < 4 || p.height < 3 || (p.width & 1) || ((p.px3 || p.planar) && kind.out16)
+      || (p.px3 && p.planar))
     return hipErrorInvalidValue;
-  if (!stage && !kind.mhc && kind.in8 && !kind.out16 && !p.px3)        /* the production kernels' */
+  if (!stage && !kind.mhc && kind.in8 && !kind.out16 && !p.px3 && !p.planar)        /* the production kernels' */
     return hipErrorInvalidValue;
   ColourParams q;               /* q.d alone is the argument of the plain kernels */
   q.d = p;

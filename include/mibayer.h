@@ -69,6 +69,8 @@ extern "C" {
 /* 5, later additive: mosaic zone statistics -- struct mibayer_stats_zone and the entry points of group `stats`. */
 /* 5, later additive: packed 24-bit output -- MIBAYER_FLAG_DST_24BIT, a fifth deep flag; no struct field and no entry
  * point was added, and a cfg without the flag means what it meant. */
+/* 5, later additive: planar 8-bit output -- MIBAYER_FLAG_DST_PLANAR, a sixth deep flag; no struct field and no entry
+ * point was added, and a cfg without the flag means what it meant. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -193,7 +195,8 @@ typedef struct mibayer_cfg {
 #define MIBAYER_FLAG_HIPGRAPH_CHAIN 4u
 
 /* Deep samples (additive within version 5: flags only, mibayer_cfg keeps its fields).  A context with any of the
- * four flags below, or MIBAYER_FLAG_DST_24BIT (a paragraph of its own further down), is a DEEP context; the algorithm
+ * four flags below, or MIBAYER_FLAG_DST_24BIT or MIBAYER_FLAG_DST_PLANAR (paragraphs of their own further down), is a
+ * DEEP context; the algorithm
  * is the one of the 8-bit path on wider integers:
  *   input   one 16-bit word per sample (little-endian; big-endian with MIBAYER_FLAG_SRC_BIG_ENDIAN), masked to its
  *           low `bits` bits -- everything above them is ignored; MIBAYER_FLAG_SRC_BITS(0) = the 8-bit mosaic;
@@ -239,6 +242,33 @@ typedef struct mibayer_cfg {
  * context with the flag runs the strip kernel instead of the production kernels; its bytes are theirs.  (Bit 21: bits
  * 17, 18 and 20 stay unknown flags, MIBAYER_ERR_ARG, as they have been.) */
 #define MIBAYER_FLAG_DST_24BIT (1u << 21)
+
+/* Planar 8-bit output (additive within version 5: a flag only): three planes of 8-bit samples, (3, height, width) as
+ * tensor code takes it (NCHW) -- no interleaved frame written, and no second pass to transpose it.  A sixth deep flag:
+ * a context that carries it is a DEEP context and everything said of deep contexts above holds (one kernel shape, no
+ * plans, variant must be 0; MIBAYER_FLAG_HIPGRAPH is accepted and the host path runs without graphs; mibayer_autotune[_list],
+ * mibayer_set_plan[_for], mibayer_plan_selectors and mibayer_launch_geometry return MIBAYER_ERR_ARG), except that
+ * mibayer_fill_synthetic works when the mosaic is 8-bit; mibayer_ctx_variant_name names the strip kernel.
+ *   output  a frame is three planes, each `height` rows of dst_stride bytes; plane k starts at
+ *           dst + k * dst_stride * height (the plane pitch is not configurable: GStreamer's GBR / RGBP / BGRP layout).
+ *           (r_off, g_off, b_off) are the PLANE INDICES of R, G and B, any permutation of (0, 1, 2): RGBP = (0,1,2),
+ *           BGRP = (2,1,0), GBR = (2,0,1); anything else is MIBAYER_ERR_LAYOUT.
+ *   values  byte (y, x) of the R plane is byte 0 of pixel (y, x) of the SAME cfg with RGBx (0,1,2) and without the
+ *           flag, G is byte 1, B is byte 2: the reference's bytes for bilinear on an 8-bit mosaic, v >> (bits - 8) for deep
+ *           mosaics, the MHC filters' and the colour stage's o >> 8 alike.
+ *   strides dst_stride default ROUND_UP_4 (width); >= width and a multiple of 4, else MIBAYER_ERR_GEOMETRY.  Only the
+ *           first `width` bytes of a row of a plane are written, on the device paths and on the host path alike: with
+ *           width % 4 == 2 a row ends two bytes before the default stride, and those two bytes (like every byte of a
+ *           wider stride's padding) keep what they held.
+ *   sizes   a frame is 3 * dst_stride * height bytes: what a batch's dst_frame_bytes must at least be, what the host
+ *           path's `dst` holds, and where d_dsts[f] of a list launch points (the base of frame f's three planes).
+ *           Device pointers and frame pitches: multiples of 4, as above.
+ * Goes with MIBAYER_FLAG_SRC_BITS (10/12/14/16), _SRC_BIG_ENDIAN, MIBAYER_FLAG_MHC, MIBAYER_FLAG_COLOUR and the
+ * statistics; with MIBAYER_FLAG_DST_16BIT, _DST_BIG_ENDIAN, MIBAYER_FLAG_DST_24BIT or MIBAYER_FLAG_RGB2BAYER it is
+ * MIBAYER_ERR_ARG (16-bit planes do not exist yet).  Geometry as the 8-bit path (even width >= 4, height >= 3),
+ * width <= 2^26 as for the other deep flags.  A plain 8-bit bilinear context with the flag runs the strip kernel
+ * instead of the production kernels; its bytes are theirs.  (Bit 22: bits 17, 18, 20, 24 and 31 stay unknown flags.) */
+#define MIBAYER_FLAG_DST_PLANAR (1u << 22)
 
 /* Malvar-He-Cutler demosaic (additive within version 5: a flag only).  Instead of the reference's bilinear average, the
  * gradient-corrected linear interpolation of Malvar, He and Cutler (ICASSP 2004): fewer zipper artefacts and colour
