@@ -180,6 +180,50 @@ def stats_grey_world(zones, pattern, black=None):
     return rc, tuple(gains)
 
 
+HIST_BINS = 256
+
+
+class Hist(ctypes.Structure):
+    """struct mibayer_hist (include/mibayer.h): bin[site][b], site s = 2 (y & 1) + (x & 1)"""
+    _fields_ = [("bin", (ctypes.c_uint32 * HIST_BINS) * 4)]
+
+
+# numpy view of one Hist: a (4, 256) array of HIST_DTYPE
+HIST_DTYPE = np.dtype(np.uint32)
+HIST_SHAPE = (4, HIST_BINS)
+
+
+def _hist_arg(hist):
+    hist = np.ascontiguousarray(hist, HIST_DTYPE)
+    assert hist.shape == HIST_SHAPE
+    return hist
+
+
+def hist_percentile(hist, pattern, colour, fraction):
+    """mibayer_hist_percentile: (ok, bin) of colour 0 / 1 / 2 = R / G / B or 3 = all sites (no device needed)"""
+    hist = _hist_arg(hist)
+    b = ctypes.c_int(0)
+    pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
+    rc = lib().mibayer_hist_percentile(_ptr(hist), pat, int(colour), float(fraction), ctypes.byref(b))
+    if rc < 0:
+        raise MibayerError(rc, "mibayer_hist_percentile")
+    return rc, b.value
+
+
+def hist_exposure(hist, pattern, depth, black, gains, fraction, target, max_gain):
+    """mibayer_hist_exposure: (ok, exposure factor); black / gains may be None (no device needed)"""
+    hist = _hist_arg(hist)
+    x = ctypes.c_double(0.0)
+    b = None if black is None else (ctypes.c_double * 3)(*[float(v) for v in black])
+    g = None if gains is None else (ctypes.c_double * 3)(*[float(v) for v in gains])
+    pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
+    rc = lib().mibayer_hist_exposure(_ptr(hist), pat, int(depth), b, g, float(fraction), float(target),
+                                     float(max_gain), ctypes.byref(x))
+    if rc < 0:
+        raise MibayerError(rc, "mibayer_hist_exposure")
+    return rc, x.value
+
+
 class PoolCfg(ctypes.Structure):
     """struct mibayer_pool_cfg (include/mibayer.h)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("stream", Cfg), ("ndevices", ctypes.c_int32),
@@ -302,6 +346,18 @@ ABI = {
     "mibayer_pool_frame_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "mibayer_stats_grey_world": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double)]),
+    "mibayer_hist_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "mibayer_set_hist": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mibayer_frame_hist": (ctypes.c_int, [_vp, _vp]),
+    "mibayer_pool_set_hist": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int]),
+    "mibayer_pool_frame_hist": (ctypes.c_int, [_vp, _vp]),
+    "mibayer_hist_percentile": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                               ctypes.POINTER(ctypes.c_int)]),
+    "mibayer_hist_exposure": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
 }
 
 
@@ -440,6 +496,16 @@ class Pool:
         """mibayer_pool_frame_stats: (zones_y, zones_x) STATS_DTYPE array of the frame wait() handed back last"""
         out = np.zeros(self._zones, STATS_DTYPE)
         _check(lib().mibayer_pool_frame_stats(self._h, _ptr(out), out.size), "mibayer_pool_frame_stats")
+        return out
+
+    def set_hist(self, on, window=(0, 0, 0, 0)):
+        """mibayer_pool_set_hist: a histogram of `window` (x0, y0, w, h) for the frames submitted from now on"""
+        _check(lib().mibayer_pool_set_hist(self._h, int(bool(on)), *window), "mibayer_pool_set_hist")
+
+    def frame_hist(self):
+        """mibayer_pool_frame_hist: (4, 256) HIST_DTYPE array of the frame wait() handed back last"""
+        out = np.zeros(HIST_SHAPE, HIST_DTYPE)
+        _check(lib().mibayer_pool_frame_hist(self._h, _ptr(out)), "mibayer_pool_frame_hist")
         return out
 
     def submit(self, src, dst, tag=0):
@@ -593,6 +659,49 @@ class Context:
             self.device_free(d_src)
             self.device_free(d_stats)
         return out.view(STATS_DTYPE).reshape(n, zones_y, zones_x)
+
+    # -- mosaic histogram -------------------------------------------------------------------
+    def hist_device(self, d_src, d_hist, window=(0, 0, 0, 0), nframes=1, src_frame_bytes=None, stream="ctx"):
+        """mibayer_hist_device: d_hist receives nframes Hist (4096 bytes each) of `window` (x0, y0, w, h)"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        _check(lib().mibayer_hist_device(self._h, _vp(d_src), src_frame_bytes or self.src_bytes, nframes, *window,
+                                         _vp(d_hist), _vp(s)), "mibayer_hist_device")
+
+    def set_hist(self, on, window=(0, 0, 0, 0)):
+        """mibayer_set_hist: a histogram of `window` for the host-path frames accepted from now on"""
+        _check(lib().mibayer_set_hist(self._h, int(bool(on)), *window), "mibayer_set_hist")
+
+    def frame_hist(self):
+        """mibayer_frame_hist: (4, 256) HIST_DTYPE array of the frame handed back last"""
+        out = np.zeros(HIST_SHAPE, HIST_DTYPE)
+        _check(lib().mibayer_frame_hist(self._h, _ptr(out)), "mibayer_frame_hist")
+        return out
+
+    def hist_batch_via_device(self, frames, window=(0, 0, 0, 0), src_frame_bytes=None, src_offset=0):
+        """frames: (N, ...) on the host, each src_frame_bytes (default: one frame) long -> (N, 4, 256) HIST_DTYPE
+        through ONE mibayer_hist_device launch.  d_hist is pre-filled with junk and followed by a guard that must
+        survive; the mosaic starts src_offset bytes into its allocation"""
+        frames = np.ascontiguousarray(frames)
+        n = frames.shape[0]
+        frames = frames.view(np.uint8).reshape(n, -1)
+        pitch = src_frame_bytes or self.src_bytes
+        assert frames.shape[1] == pitch
+        nb = n * ctypes.sizeof(Hist)
+        guard = 256
+        d_src = self.device_alloc(n * pitch + src_offset)
+        d_hist = self.device_alloc(nb + guard)
+        try:
+            self.to_device(d_src + src_offset, frames)
+            self.to_device(d_hist, np.full(nb + guard, 0xA5, np.uint8))
+            self.hist_device(d_src + src_offset, d_hist, window, n, pitch)
+            self.sync()
+            out = self.from_device(d_hist, nb + guard)
+        finally:
+            self.device_free(d_src)
+            self.device_free(d_hist)
+        if not (out[nb:] == 0xA5).all():
+            raise AssertionError("mibayer_hist_device wrote past the last histogram")
+        return out[:nb].view(HIST_DTYPE).reshape((n,) + HIST_SHAPE)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):

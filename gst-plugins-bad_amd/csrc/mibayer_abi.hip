@@ -137,6 +137,11 @@ struct StatsGrid {
   uint32_t lo = 0, hi = 0;
 };
 constexpr size_t kStatsSlotBytes = (size_t) MIBAYER_STATS_MAX_ZONES * MIBAYER_STATS_MAX_ZONES * sizeof (mibayer_stats_zone);
+/* a histogram window (mibayer_set_hist); on = 0: histograms off.  The histogram of a slot lies behind its zones, in the
+ * same device and pinned buffers */
+struct HistWin {
+  int on = 0, x0 = 0, y0 = 0, w = 0, h = 0;
+};
 
 constexpr int kMaxHostBands = 8;
 constexpr int kInverseBandUnit = 16;    /* rows; a multiple of every rows-per-block of the rgb2bayer kernel */
@@ -174,6 +179,7 @@ struct Slot {
   StatsGrid grid;
   mibayer_stats_zone *d_stats = nullptr;
   mibayer_stats_zone *h_stats = nullptr;
+  HistWin win;                    /* mibayer_set_hist: likewise */
 };
 
 int device_count_cached ()
@@ -323,6 +329,9 @@ struct mibayer_ctx {
   StatsGrid stats_grid;
   StatsGrid last_grid;
   std::vector<mibayer_stats_zone> last_zones;
+  HistWin hist_win;                     /* mibayer_set_hist / mibayer_frame_hist: likewise, under stats_mu */
+  bool last_hist_on = false;
+  mibayer_hist last_hist;
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -1854,6 +1863,172 @@ extern "C" int mibayer_launch_geometry (const mibayer_ctx *c, int nframes,
   return MIBAYER_OK;
 }
 
+/* ---- mosaic histogram (group `hist`) ------------------------------------------------ */
+
+static mibayer_hist *slot_hist (mibayer_stats_zone *base)
+{
+  return (mibayer_hist *) ((uint8_t *) base + kStatsSlotBytes);
+}
+
+/* the argument checks of mibayer_hist_device / mibayer_set_hist (include/mibayer.h) and the kernel's arguments */
+static int hist_params (const mibayer_ctx *c, const HistWin &w, HistParams *q)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  const mibayer_cfg &f = c->cfg;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  int x0 = w.x0, y0 = w.y0, ww = w.w, wh = w.h;
+  if (x0 == 0 && y0 == 0 && ww == 0 && wh == 0) {
+    ww = f.width;
+    wh = f.height;
+  }
+  if (x0 < 0 || y0 < 0 || (x0 & 1) || (ww & 1) || ww < 2 || wh < 1 || ww > f.width - x0 || wh > f.height - y0)
+    return MIBAYER_ERR_ARG;
+  if ((unsigned long long) (ww / 2) * (unsigned long long) ((wh + 1) / 2) > 0xffffffffull)
+    return MIBAYER_ERR_GEOMETRY;
+  memset (q, 0, sizeof *q);
+  q->src_stride = f.src_stride;
+  q->in8 = bits == 0;
+  q->in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
+  q->mask2 = (bits ? (1u << bits) - 1u : 255u) * 0x00010001u;
+  q->shift = bits ? bits - 8 : 0;
+  q->x0 = x0;
+  q->x1 = x0 + ww;
+  q->y0 = y0;
+  q->y1 = y0 + wh;
+  return MIBAYER_OK;
+}
+
+/* zeroes `d_hist` and launches the kernel over `nframes` frames on `stream` */
+static int enqueue_hist (HistParams &q, const void *d_src, size_t src_frame_bytes, int nframes, mibayer_hist *d_hist,
+    hipStream_t stream)
+{
+  q.src = (const uint8_t *) d_src;
+  q.src_frame_bytes = src_frame_bytes;
+  q.hist = (uint32_t *) d_hist;
+  HIP_TRY (hipMemsetAsync (d_hist, 0, (size_t) nframes * sizeof (mibayer_hist), stream));
+  HIP_TRY (launch_hist (q, nframes, stream));
+  return MIBAYER_OK;
+}
+
+static void mark_dirty (mibayer_ctx *c, hipStream_t s);
+
+extern "C" int mibayer_hist_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes, int x0,
+    int y0, int w, int h, mibayer_hist *d_hist, void *hip_stream)
+{
+  if (!c || !d_src || !d_hist || nframes < 0)
+    return MIBAYER_ERR_ARG;
+  const HistWin win = { 1, x0, y0, w, h };
+  HistParams q;
+  const int rc = hist_params (c, win, &q);
+  if (rc != MIBAYER_OK)
+    return rc;
+  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3)))
+    return MIBAYER_ERR_GEOMETRY;
+  if ((((uintptr_t) d_src) | ((uintptr_t) d_hist)) & 3)
+    return MIBAYER_ERR_ARG;
+  if (nframes == 0)
+    return MIBAYER_OK;
+  DeviceGuard guard (c->device);
+  if (!guard.ok)
+    return MIBAYER_ERR_HIP;
+  Range r ("mibayer:hist_device");
+  mark_dirty (c, (hipStream_t) hip_stream);
+  return enqueue_hist (q, d_src, src_frame_bytes, nframes, d_hist, (hipStream_t) hip_stream);
+}
+
+extern "C" int mibayer_set_hist (mibayer_ctx *c, int on, int x0, int y0, int w, int h)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  HistWin win;
+  if (on) {
+    win = { 1, x0, y0, w, h };
+    HistParams q;
+    const int rc = hist_params (c, win, &q);
+    if (rc != MIBAYER_OK)
+      return rc;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->hist_win = win;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_frame_hist (mibayer_ctx *c, mibayer_hist *out)
+{
+  if (!c || !out)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (!c->last_hist_on)
+    return MIBAYER_ERR_EMPTY;
+  *out = c->last_hist;
+  return MIBAYER_OK;
+}
+
+/* colour (0 = R, 1 = G, 2 = B) of site s = 2 (y & 1) + (x & 1), per Bayer order */
+static const int kSiteColour[4][4] = { { 2, 1, 1, 0 }, { 1, 2, 0, 1 }, { 1, 0, 2, 1 }, { 0, 1, 1, 2 } };
+
+extern "C" int mibayer_hist_percentile (const mibayer_hist *hist, int pattern, int colour, double fraction, int *bin)
+{
+  if (!hist || !bin || pattern < MIBAYER_BGGR || pattern > MIBAYER_RGGB || colour < 0 || colour > 3
+      || !(fraction >= 0.0 && fraction <= 1.0))
+    return MIBAYER_ERR_ARG;
+  uint64_t pooled[MIBAYER_HIST_BINS], n = 0;
+  for (int b = 0; b < MIBAYER_HIST_BINS; b++) {
+    pooled[b] = 0;
+    for (int site = 0; site < 4; site++)
+      if (colour == 3 || kSiteColour[pattern][site] == colour)
+        pooled[b] += hist->bin[site][b];
+    n += pooled[b];
+  }
+  *bin = -1;
+  if (n == 0)
+    return 0;
+  uint64_t r = (uint64_t) ceil (fraction * (double) n);
+  r = r < 1 ? 1 : r;
+  uint64_t cum = 0;
+  for (int b = 0; b < MIBAYER_HIST_BINS; b++) {
+    cum += pooled[b];
+    if (cum >= r) {
+      *bin = b;
+      return 1;
+    }
+  }
+  *bin = MIBAYER_HIST_BINS - 1;         /* (r rounded above n: counts beyond 2^53) */
+  return 1;
+}
+
+extern "C" int mibayer_hist_exposure (const mibayer_hist *hist, int pattern, int depth, const double black[3],
+    const double gains[3], double fraction, double target, double max_gain, double *exposure)
+{
+  if (!hist || !exposure || depth < 8 || depth > 16 || (depth & 1) || !(target > 0.0 && target <= 1.0)
+      || !(max_gain >= 1.0 && max_gain <= 15.99))
+    return MIBAYER_ERR_ARG;
+  const double max = (double) ((1u << depth) - 1u);
+  double level = 0.0;
+  bool ok = true;
+  for (int k = 0; k < 3; k++) {
+    int b;
+    const int rc = mibayer_hist_percentile (hist, pattern, k, fraction, &b);
+    if (rc < 0)
+      return rc;
+    const double bk = black ? black[k] : 0.0;
+    if (rc == 0 || !(bk < max)) {
+      ok = false;
+      continue;
+    }
+    const double v = (double) (b + 1) * (double) (1u << (depth - 8)) - 1.0;
+    const double l = (gains ? gains[k] : 1.0) * fmax (v - bk, 0.0) / (max - bk);
+    level = l > level ? l : level;
+  }
+  *exposure = 1.0;
+  if (!ok || !(level > 0.0))
+    return 0;
+  const double x = target / level;
+  *exposure = x < 1.0 / 16 ? 1.0 / 16 : x > max_gain ? max_gain : x;
+  return 1;
+}
+
 /* ---- mosaic zone statistics (group `stats`) -------------------------------------------- */
 
 /* the argument checks of mibayer_stats_device / mibayer_set_stats (include/mibayer.h) and the kernel's arguments */
@@ -1895,8 +2070,6 @@ static int enqueue_stats (StatsParams &q, const void *d_src, size_t src_frame_by
   HIP_TRY (launch_stats (q, nframes, stream));
   return MIBAYER_OK;
 }
-
-static void mark_dirty (mibayer_ctx *c, hipStream_t s);
 
 extern "C" int mibayer_stats_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes,
     int zones_x, int zones_y, uint32_t lo, uint32_t hi, mibayer_stats_zone *d_stats, void *hip_stream)
@@ -1965,19 +2138,30 @@ static int slot_take_stats (mibayer_ctx *c, Slot &s)
   {
     std::lock_guard<std::mutex> lk (c->stats_mu);
     s.grid = c->stats_grid;
+    s.win = c->hist_win;
   }
-  if (s.grid.zones_x == 0)
+  if (s.grid.zones_x == 0 && !s.win.on)
     return MIBAYER_OK;
   if (!s.d_stats)
-    HIP_TRY (hipMalloc ((void **) &s.d_stats, kStatsSlotBytes));
+    HIP_TRY (hipMalloc ((void **) &s.d_stats, kStatsSlotBytes + sizeof (mibayer_hist)));
   if (!s.h_stats)
-    HIP_TRY (hipHostMalloc ((void **) &s.h_stats, kStatsSlotBytes, hipHostMallocDefault));
+    HIP_TRY (hipHostMalloc ((void **) &s.h_stats, kStatsSlotBytes + sizeof (mibayer_hist), hipHostMallocDefault));
   return MIBAYER_OK;
 }
 
 /* the statistics launch of the frame in slot `s` on the compute queue, behind the upload of its last row */
 static int slot_launch_stats (mibayer_ctx *c, Slot &s)
 {
+  if (s.win.on) {
+    HistParams h;
+    const int rc = hist_params (c, s.win, &h);
+    if (rc != MIBAYER_OK)
+      return rc;
+    Range r ("mibayer:hist");
+    const int hrc = enqueue_hist (h, s.d_src, c->src_bytes, 1, slot_hist (s.d_stats), c->s_compute);
+    if (hrc != MIBAYER_OK)
+      return hrc;
+  }
   if (s.grid.zones_x == 0)
     return MIBAYER_OK;
   StatsParams q;
@@ -1991,6 +2175,9 @@ static int slot_launch_stats (mibayer_ctx *c, Slot &s)
 /* ... and their download on the download queue, behind the event of that launch */
 static int slot_download_stats (mibayer_ctx *c, Slot &s)
 {
+  if (s.win.on)
+    HIP_TRY (hipMemcpyAsync (slot_hist (s.h_stats), slot_hist (s.d_stats), sizeof (mibayer_hist), hipMemcpyDeviceToHost,
+            c->s_d2h));
   if (s.grid.zones_x == 0)
     return MIBAYER_OK;
   HIP_TRY (hipMemcpyAsync (s.h_stats, s.d_stats,
@@ -2002,6 +2189,9 @@ static int slot_download_stats (mibayer_ctx *c, Slot &s)
 static void slot_retire_stats (mibayer_ctx *c, const Slot &s)
 {
   std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->last_hist_on = s.win.on != 0;
+  if (s.win.on)
+    c->last_hist = *slot_hist (s.h_stats);
   c->last_grid = s.grid;
   if (s.grid.zones_x == 0)
     c->last_zones.clear ();
@@ -2014,8 +2204,6 @@ extern "C" int mibayer_stats_grey_world (const mibayer_stats_zone *zones, int nz
 {
   if (!zones || !gains || nzones < 1 || pattern < MIBAYER_BGGR || pattern > MIBAYER_RGGB)
     return MIBAYER_ERR_ARG;
-  /* colour (0 = R, 1 = G, 2 = B) of site s = 2 (y & 1) + (x & 1), per Bayer order */
-  static const int kSiteColour[4][4] = { { 2, 1, 1, 0 }, { 1, 2, 0, 1 }, { 1, 0, 2, 1 }, { 0, 1, 1, 2 } };
   unsigned long long sum[3] = { 0, 0, 0 }, n[3] = { 0, 0, 0 };
   for (int z = 0; z < nzones; z++)
     for (int site = 0; site < 4; site++) {
@@ -2406,7 +2594,7 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
     return rc;
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
   /* (the captured graphs hold the demosaic launch only: a frame with statistics is launched without them) */
-  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0;
+  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on;
   if (want_graph && c->graph_mode == 1
       && (size_t) c->cfg.dst_stride == row_bytes) {
     rc = graph_submit (c, s, src, dst);

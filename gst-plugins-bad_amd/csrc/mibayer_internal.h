@@ -330,6 +330,31 @@ struct StatsParams {
 /* one launch over `nframes` frames; p.stats must have been zeroed on the stream before */
 hipError_t launch_stats (const StatsParams &p, int nframes, hipStream_t stream);
 
+/* Mosaic histogram (mosaic_hist_kernel; include/mibayer.h, group `hist`): read-only over the mosaic, one kernel for both
+ * sample widths and byte orders (uniform run-time branches) */
+constexpr int kHistReps = 8;            /* LDS replicas of the [site][bin] table, one per lane & 7 */
+constexpr int kHistAhead = 8;           /* dword loads in flight per lane = depth of the row loop */
+constexpr int kHistMaxRows = 256;       /* rows a workgroup walks at most (256 KiB read per 4 KiB merged), even */
+constexpr int kHistMinRows = 16;        /* ... and at least, when the launch is too small to fill the device otherwise */
+constexpr int kHistSpread = 512;        /* workgroups a launch is spread over before the rows per workgroup grow */
+struct HistParams {
+  const uint8_t *src;
+  unsigned long long src_frame_bytes;
+  uint32_t *hist;               /* nframes x [site 4][bin 256] */
+  int src_stride;
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a source dword: identity or a byte swap per 16-bit word */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  int shift;                    /* depth - 8 */
+  int x0, x1, y0, y1;           /* the window: columns [x0, x1), rows [y0, y1) */
+  /* filled by launch_hist */
+  int g0, g1;                   /* dwords of a row that hold columns of the window */
+  int seg_rows;                 /* rows a workgroup walks, even */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row of the window */
+};
+/* one launch over `nframes` frames; p.hist must have been zeroed on the stream before */
+hipError_t launch_hist (const HistParams &p, int nframes, hipStream_t stream);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

@@ -2410,6 +2410,113 @@ hipError_t launch_stats (const StatsParams &p, int nframes, hipStream_t stream)
 }
 
 /* ------------------------------------------------------------------------- */
+/* mosaic histogram                                                            */
+/* ------------------------------------------------------------------------- */
+/* 256 bins per CFA site over a window of the mosaic (include/mibayer.h, group `hist`).  Read-only over the mosaic.  A
+ * workgroup is four waves side by side, each on a strip of 64 dwords, walking seg_rows rows of the window, kHistAhead
+ * dword loads in flight per lane.  Every sample is one no-return LDS atomic into the workgroup's table; the table is
+ * kept kHistReps times, lane l adding to replica l & 7, so that a wave whose samples all fall into one bin (a flat wall,
+ * a clipped sky, a black frame) meets an 8-fold serialisation and not a 64-fold one.  Replica r keeps entry e at
+ * r * 1024 + (e ^ 8 r): the eight copies of one entry lie in eight different banks, and a wave reading consecutive
+ * entries of one replica reads 64 different banks.  The two samples of a dword that share a site (8-bit mosaic, both
+ * column pairs inside) go as one atomic of 2 when they share the bin.  After a barrier thread t sums the replicas of
+ * entries t, t + 256, ... and issues one no-return global atomic per non-zero entry: consecutive lanes, consecutive
+ * counters.  Integer additions: the result does not depend on their order. */
+__global__ void __launch_bounds__ (256)
+mosaic_hist_kernel (HistParams p)
+{
+  __shared__ uint32_t tab[kHistReps * 1024];
+  for (int i = (int) threadIdx.x; i < kHistReps * 1024; i += 256)
+    tab[i] = 0;
+  __syncthreads ();
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int ya = p.y0 + (int) blockIdx.y * p.seg_rows;  /* < y1 (launch_hist) */
+  const int yb = ya + p.seg_rows < p.y1 ? ya + p.seg_rows : p.y1;
+  const int g = p.g0 + (int) (strip * 256u + threadIdx.x);      /* dword of the row */
+  if (g < p.g1) {
+    const int c0 = p.in8 ? 4 * g : 2 * g;               /* its first column: even; a column pair is in or out as a whole */
+    const bool in0 = c0 >= p.x0 && c0 < p.x1;
+    const bool in1 = p.in8 && c0 + 2 >= p.x0 && c0 + 2 < p.x1;
+    const bool both = in0 && in1;
+    const uint32_t swz = (threadIdx.x & (kHistReps - 1)) << 3;
+    uint32_t *rep = tab + (threadIdx.x & (kHistReps - 1)) * 1024;
+    const uint8_t *col = p.src + frame * p.src_frame_bytes + 4 * (size_t) g;
+    for (int y = ya; y < yb; y += kHistAhead) {         /* uniform over the workgroup */
+      uint32_t d[kHistAhead];
+#pragma unroll
+      for (int i = 0; i < kHistAhead; i++)
+        d[i] = y + i < yb
+            ? __builtin_nontemporal_load ((const uint32_t *) (col + (size_t) (y + i) * (size_t) p.src_stride)) : 0u;
+#pragma unroll
+      for (int i = 0; i < kHistAhead; i++) {
+        if (y + i >= yb)
+          break;
+        const uint32_t sb = (uint32_t) ((y + i) & 1) * 512u;    /* site 2 (y & 1) + column parity */
+        uint32_t b0, b1, b2, b3;
+        if (p.in8) {
+          b0 = d[i] & 0xffu;
+          b1 = (d[i] >> 8) & 0xffu;
+          b2 = (d[i] >> 16) & 0xffu;
+          b3 = d[i] >> 24;
+        } else {
+          const uint32_t m = __builtin_amdgcn_perm (d[i], d[i], p.in_sel) & p.mask2;
+          b0 = b2 = (m & 0xffffu) >> p.shift;
+          b1 = b3 = m >> (16 + p.shift);
+        }
+        const bool e02 = both && b0 == b2, e13 = both && b1 == b3;
+        if (in0) {
+          atomicAdd (&rep[(sb + b0) ^ swz], e02 ? 2u : 1u);
+          atomicAdd (&rep[(sb + 256u + b1) ^ swz], e13 ? 2u : 1u);
+        }
+        if (in1 && !e02)
+          atomicAdd (&rep[(sb + b2) ^ swz], 1u);
+        if (in1 && !e13)
+          atomicAdd (&rep[(sb + 256u + b3) ^ swz], 1u);
+      }
+    }
+  }
+  __syncthreads ();
+  uint32_t *out = p.hist + (size_t) frame * 1024u;
+  for (uint32_t e = threadIdx.x; e < 1024u; e += 256u) {
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < (uint32_t) kHistReps; r++)
+      n += tab[r * 1024u + (e ^ (r << 3))];
+    if (n)
+      atomicAdd (out + e, n);
+  }
+}
+
+hipError_t launch_hist (const HistParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.x0 < 0 || (p.x0 & 1) || (p.x1 & 1) || p.x1 < p.x0 + 2 || p.y0 < 0 || p.y1 < p.y0 + 1 || p.shift < 0 || p.shift > 8)
+    return hipErrorInvalidValue;        /* (a column pair half inside, a bin past the table) */
+  HistParams q = p;
+  q.g0 = p.in8 ? p.x0 / 4 : p.x0 / 2;
+  q.g1 = p.in8 ? (p.x1 + 3) / 4 : p.x1 / 2;
+  const long long strips = (q.g1 - q.g0 + 255) / 256;
+  /* Rows per workgroup.  A workgroup merges up to 4 KiB of counters with global atomics and reads seg_rows KiB of mosaic
+   * (a strip is 1 KiB wide): at kHistMaxRows the merge is 1/64 of its bytes.  A small launch (one frame on the host path)
+   * is cut finer, down to kHistMinRows, until it has kHistSpread workgroups. */
+  const long long h = p.y1 - p.y0;
+  long long rows = h * strips * nframes / kHistSpread;
+  rows = rows < kHistMinRows ? kHistMinRows : rows > kHistMaxRows ? kHistMaxRows : rows;
+  if ((h + rows - 1) / rows > 65535)
+    rows = (h + 65534) / 65535;
+  rows = (rows + 1) & ~1LL;
+  const long long gy = (h + rows - 1) / rows;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535)
+    return hipErrorInvalidValue;
+  q.seg_rows = (int) rows;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  hipLaunchKernelGGL (mosaic_hist_kernel, dim3 ((unsigned) (strips * nframes), (unsigned) gy), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

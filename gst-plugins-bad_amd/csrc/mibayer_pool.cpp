@@ -59,6 +59,9 @@
 /* ... and so are the statistics': a pool over such a double refuses mibayer_pool_set_stats */
 #pragma weak mibayer_set_stats
 #pragma weak mibayer_frame_stats
+/* ... and the histogram's: mibayer_pool_set_hist is refused there too */
+#pragma weak mibayer_set_hist
+#pragma weak mibayer_frame_hist
 
 #include <sched.h>
 
@@ -77,10 +80,14 @@
 
 namespace {
 
+/* what mibayer_pool_set_stats and mibayer_pool_set_hist asked for, together: one record per frame carries both */
 struct StatsGrid {
-  int zones_x, zones_y;
+  int zones_x, zones_y;         /* (0, 0): no zones */
   uint32_t lo, hi;
+  int hist, x0, y0, w, h;       /* hist = 0: no histogram */
 };
+/* a frame's histogram rides behind its zones in the same vector, as it does in a context's slot */
+constexpr size_t kHistZones = sizeof (mibayer_hist) / sizeof (mibayer_stats_zone);
 
 enum FrameState {
   F_DIRECT,     /* in the ring of its shard's context, submitted by the streaming thread */
@@ -166,21 +173,34 @@ void apply_stats (Shard *sh, const Frame *f)
 {
   if (f->grid == sh->applied_grid || !mibayer_set_stats)
     return;
-  const StatsGrid off = { 0, 0, 0, 0 };
+  const StatsGrid off = {};
   const StatsGrid *g = f->grid ? f->grid.get () : &off;
-  if (mibayer_set_stats (sh->ctx, g->zones_x, g->zones_y, g->lo, g->hi) == MIBAYER_OK)
+  bool ok = mibayer_set_stats (sh->ctx, g->zones_x, g->zones_y, g->lo, g->hi) == MIBAYER_OK;
+  if (mibayer_set_hist)
+    ok = mibayer_set_hist (sh->ctx, g->hist, g->x0, g->y0, g->w, g->h) == MIBAYER_OK && ok;
+  if (ok)
     sh->applied_grid = f->grid;
+}
+
+/* the zones, then the histogram, of the frame the context of `sh` handed back last; empty when it has neither */
+void read_stats (Shard *sh, const StatsGrid *g, std::vector<mibayer_stats_zone> *z)
+{
+  z->clear ();
+  if (!g || !mibayer_frame_stats)
+    return;
+  const size_t nz = (size_t) g->zones_x * (size_t) g->zones_y;
+  z->resize (nz + (g->hist ? kHistZones : 0));
+  bool ok = nz == 0 || mibayer_frame_stats (sh->ctx, z->data (), (int) nz) == MIBAYER_OK;
+  if (g->hist)
+    ok = ok && mibayer_frame_hist && mibayer_frame_hist (sh->ctx, (mibayer_hist *) (z->data () + nz)) == MIBAYER_OK;
+  if (!ok)
+    z->clear ();
 }
 
 /* the context of `sh` has just handed the frame back to this thread: keep its zones with the frame */
 void fetch_stats (Shard *sh, Frame *f)
 {
-  f->zones.clear ();
-  if (!f->grid || !mibayer_frame_stats)
-    return;
-  f->zones.resize ((size_t) f->grid->zones_x * (size_t) f->grid->zones_y);
-  if (mibayer_frame_stats (sh->ctx, f->zones.data (), (int) f->zones.size ()) != MIBAYER_OK)
-    f->zones.clear ();
+  read_stats (sh, f->grid.get (), &f->zones);
 }
 
 bool device_failure (int rc)
@@ -309,11 +329,8 @@ void helper_main (Shard *sh)
       if (rc == MIBAYER_OK && sh->fault_due ())
         rc = MIBAYER_ERR_HIP;
       std::vector<mibayer_stats_zone> zones;
-      if (rc == MIBAYER_OK && f->grid && mibayer_frame_stats) {
-        zones.resize ((size_t) f->grid->zones_x * (size_t) f->grid->zones_y);
-        if (mibayer_frame_stats (sh->ctx, zones.data (), (int) zones.size ()) != MIBAYER_OK)
-          zones.clear ();
-      }
+      if (rc == MIBAYER_OK)
+        read_stats (sh, f->grid.get (), &zones);
       lk.lock ();
       if (sh->ring.empty () || sh->ring.front () != f)
         continue;               /* the shard was given up meanwhile */
@@ -361,6 +378,7 @@ struct mibayer_pool {
   std::shared_ptr<const StatsGrid> grid;
   std::vector<mibayer_stats_zone> last_zones;
   bool has_zones = false;
+  std::shared_ptr<const StatsGrid> last_grid;   /* ... which says what last_zones holds */
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -700,12 +718,12 @@ extern "C" int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour
 
 /* The statistics grid of the frames submitted from now on, kept with each frame like the colour stage (apply_stats);
  * the range checks are the context layer's: the grid is tried on the first shard's context -- whose own frames carry
- * theirs, and get it back before they are handed over -- so a bad one is refused here and not frames later. */
-extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zones_y, uint32_t lo, uint32_t hi)
+ * theirs, and get it back before they are handed over -- so a bad one is refused here and not frames later.  Both
+ * setters end here: `g` is what the frames submitted from now on get (neither zones nor a histogram: NULL), and
+ * `hist_call` says which half of it is new. */
+static int pool_set_grid (mibayer_pool *pool, const StatsGrid &g, bool hist_call)
 {
-  if (!pool || !mibayer_set_stats || !mibayer_frame_stats)
-    return MIBAYER_ERR_ARG;
-  if (zones_x == 0 && zones_y == 0) {
+  if (g.zones_x == 0 && g.zones_y == 0 && !g.hist) {
     pool->grid.reset ();
     return MIBAYER_OK;
   }
@@ -715,13 +733,13 @@ extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zone
       probe = sh;
       break;
     }
-  const StatsGrid g = { zones_x, zones_y, lo, hi };
   if (probe) {
-    const int rc = mibayer_set_stats (probe->ctx, zones_x, zones_y, lo, hi);
+    const int rc = hist_call ? mibayer_set_hist (probe->ctx, g.hist, g.x0, g.y0, g.w, g.h)
+        : mibayer_set_stats (probe->ctx, g.zones_x, g.zones_y, g.lo, g.hi);
     if (rc != MIBAYER_OK)
       return rc;
-    probe->applied_grid = std::make_shared<const StatsGrid> (g);
-    pool->grid = probe->applied_grid;
+    pool->grid = std::make_shared<const StatsGrid> (g);
+    probe->applied_grid = std::make_shared<const StatsGrid> (g);        /* no frame's: apply_stats sets both halves */
     return MIBAYER_OK;
   }
   /* every context is driven by a helper thread: the same rule on the resolved configuration */
@@ -730,22 +748,63 @@ extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zone
     return MIBAYER_ERR_ARG;
   const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
   const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
-  if (zones_x < 1 || zones_x > MIBAYER_STATS_MAX_ZONES || zones_y < 1 || zones_y > MIBAYER_STATS_MAX_ZONES
-      || zones_x > f.width / 2 || zones_y > f.height / 2 || lo > hi || hi > vmax)
+  if (!hist_call && (g.zones_x | g.zones_y) && (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1
+          || g.zones_y > MIBAYER_STATS_MAX_ZONES || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.lo > g.hi
+          || g.hi > vmax))
+    return MIBAYER_ERR_ARG;
+  const bool whole = !(g.x0 | g.y0 | g.w | g.h);
+  if (hist_call && g.hist && !whole && (g.x0 < 0 || g.y0 < 0 || ((g.x0 | g.w) & 1) || g.w < 2 || g.h < 1
+          || g.w > f.width - g.x0 || g.h > f.height - g.y0))
     return MIBAYER_ERR_ARG;
   pool->grid = std::make_shared<const StatsGrid> (g);
   return MIBAYER_OK;
+}
+
+extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zones_y, uint32_t lo, uint32_t hi)
+{
+  if (!pool || !mibayer_set_stats || !mibayer_frame_stats)
+    return MIBAYER_ERR_ARG;
+  StatsGrid g = pool->grid ? *pool->grid : StatsGrid ();
+  g.zones_x = zones_x;
+  g.zones_y = zones_y;
+  g.lo = lo;
+  g.hi = hi;
+  return pool_set_grid (pool, g, false);
 }
 
 extern "C" int mibayer_pool_frame_stats (mibayer_pool *pool, mibayer_stats_zone *out, int nzones)
 {
   if (!pool || !out)
     return MIBAYER_ERR_ARG;
-  if (!pool->has_zones)
+  if (!pool->has_zones || pool->last_grid->zones_x == 0)
     return MIBAYER_ERR_EMPTY;
-  if (nzones != (int) pool->last_zones.size ())
+  if (nzones != pool->last_grid->zones_x * pool->last_grid->zones_y)
     return MIBAYER_ERR_ARG;
-  memcpy (out, pool->last_zones.data (), pool->last_zones.size () * sizeof (mibayer_stats_zone));
+  memcpy (out, pool->last_zones.data (), (size_t) nzones * sizeof (mibayer_stats_zone));
+  return MIBAYER_OK;
+}
+
+/* The histogram window of the frames submitted from now on: kept, applied and fetched with the statistics grid */
+extern "C" int mibayer_pool_set_hist (mibayer_pool *pool, int on, int x0, int y0, int w, int h)
+{
+  if (!pool || !mibayer_set_stats || !mibayer_frame_stats || !mibayer_set_hist || !mibayer_frame_hist)
+    return MIBAYER_ERR_ARG;
+  StatsGrid g = pool->grid ? *pool->grid : StatsGrid ();
+  g.hist = on ? 1 : 0;
+  g.x0 = on ? x0 : 0;
+  g.y0 = on ? y0 : 0;
+  g.w = on ? w : 0;
+  g.h = on ? h : 0;
+  return pool_set_grid (pool, g, true);
+}
+
+extern "C" int mibayer_pool_frame_hist (mibayer_pool *pool, mibayer_hist *out)
+{
+  if (!pool || !out)
+    return MIBAYER_ERR_ARG;
+  if (!pool->has_zones || !pool->last_grid->hist)
+    return MIBAYER_ERR_EMPTY;
+  memcpy (out, pool->last_zones.data () + pool->last_zones.size () - kHistZones, sizeof *out);
   return MIBAYER_OK;
 }
 
@@ -973,6 +1032,7 @@ extern "C" int mibayer_pool_wait (mibayer_pool *pool, void **tag)
   if (tag)
     *tag = f.tag;
   pool->has_zones = f.grid && !f.zones.empty ();
+  pool->last_grid = f.grid;
   pool->last_zones.swap (f.zones);
   pool->shards[(size_t) f.owner]->inflight--;
   pool->fifo.pop_front ();

@@ -281,7 +281,20 @@ element_collect_locked (GstMiBayerElement * self, GstBuffer ** outbuf,
     *gpu_rc = rc;
     return GST_FLOW_ERROR;
   }
-  if (self->awb_on) {
+  if (self->ae_on) {
+    /* exposure=auto: the frame's histogram (and, with grey-world on as well, its means first) move the gains of the
+     * frames accepted from now on */
+    mibayer_stats_zone zone;
+    mibayer_hist hist;
+    mibayer_colour colour;
+    const gboolean have_zone = self->awb_on && mibayer_pool_frame_stats (self->pool, &zone, 1) == MIBAYER_OK;
+    const gboolean have_hist = mibayer_pool_frame_hist (self->pool, &hist) == MIBAYER_OK;
+
+    if (gst_mi_auto_step (self->act.colour, (GstMiAwb *) self->awb_gain, (GstMiAe *) & self->ae_e,
+            have_zone ? &zone : NULL, have_hist ? &hist : NULL, self->format, self->src_bits ? self->src_bits : 8,
+            &colour))
+      (void) mibayer_pool_set_colour (self->pool, &colour);
+  } else if (self->awb_on) {
     /* white-balance=grey-world: the frame's means move the gains of the frames accepted from now on */
     mibayer_stats_zone zone;
     mibayer_colour colour;
@@ -470,6 +483,7 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
   self->pool_stride = 0;
   self->capacity = 0;
   self->awb_on = FALSE;
+  self->ae_on = FALSE;
 
   /* the colour stage: only when a colour property is off its default (the default output is the reference's bytes) */
   want_colour = !inverse && !gst_mi_colour_props_are_default (self->act.colour);
@@ -560,6 +574,26 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       return FALSE;
     }
     self->awb_on = TRUE;
+  }
+  if (want_colour && ((GstMiColourProps *) self->act.colour)->exposure == GST_MI_EXPOSURE_AUTO) {
+    const GstMiColourProps *props = self->act.colour;
+
+    rc = mibayer_pool_set_hist && mibayer_pool_frame_hist && mibayer_hist_exposure
+        ? mibayer_pool_set_hist (self->pool, 1, 0, 0, 0, 0) : MIBAYER_ERR_ARG;
+    if (rc != MIBAYER_OK) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up exposure=auto", LABEL (self)),
+          g_strdup_printf ("mibayer_pool_set_hist: %s", mibayer_strerror (rc)));
+      return FALSE;
+    }
+    if (!self->awb_on) {
+      self->awb_gain[0] = props->gain[0];
+      self->awb_gain[1] = props->gain[2];
+    }
+    self->ae_e = 1.0;
+    self->ae_on = TRUE;
   }
   /* a GPU that stops answering is dropped like one that reports an error, after this long */
   (void) mibayer_pool_set_wait_timeout (self->pool, self->act.timeout_ms);

@@ -83,6 +83,8 @@ struct _GstMiBayerElement
   gint capacity;                /* frames the pool may hold in flight (shrinks when a device is dropped) */
   gboolean awb_on;              /* white-balance=grey-world: the pool measures every frame (1 x 1 statistics) ... */
   gdouble awb_gain[2];          /* ... and these are the red and blue gain in use (GstMiAwb, gstmicolour.h) */
+  gboolean ae_on;               /* exposure=auto: the pool hands back the whole-frame histogram of every frame ... */
+  gdouble ae_e;                 /* ... and this is the factor on the gains in use (GstMiAe, gstmicolour.h) */
   GQueue pending;               /* PendingFrame*, oldest first */
   GQueue ready;                 /* GstBuffer*: finished outputs collected early (the pool shrank), oldest first */
   GQueue quarantine;            /* PendingFrame*: frames lost on a GPU that ran into the wait deadline; both buffers

@@ -9,6 +9,9 @@
  * white-balance=grey-world sets the flag on its own: the element measures every frame it gets back (1 x 1 mosaic zone
  * statistics, group `stats` of include/mibayer.h) and moves its red and blue gain towards the grey-world gains of that
  * frame (gst_mi_awb_step), for the frames it accepts afterwards.
+ * exposure=auto sets the flag on its own too: the element reads the whole-frame mosaic histogram (group `hist`) of
+ * every frame it gets back and moves a factor e on all three gains towards the one that puts the 99th percentile of
+ * the brightest channel at ae-target (gst_mi_auto_step); ae-speed and ae-max-gain shape the loop.
  *
  * The colour entry points of libmibayer are bound WEAKLY: the plugins also load against builds of the library
  * interface that do not have them (the test doubles of tests/check), where a non-default colour request ends in an
@@ -34,11 +37,21 @@
 #pragma weak mibayer_pool_set_stats
 #pragma weak mibayer_pool_frame_stats
 #pragma weak mibayer_stats_grey_world
+#pragma weak mibayer_hist_device
+#pragma weak mibayer_pool_set_hist
+#pragma weak mibayer_pool_frame_hist
+#pragma weak mibayer_hist_exposure
 
 enum
 {
   GST_MI_WHITE_BALANCE_MANUAL = 0,
   GST_MI_WHITE_BALANCE_GREY_WORLD
+};
+
+enum
+{
+  GST_MI_EXPOSURE_MANUAL = 0,
+  GST_MI_EXPOSURE_AUTO
 };
 
 typedef struct
@@ -50,6 +63,8 @@ typedef struct
   gdouble gamma;
   gint white_balance;           /* GST_MI_WHITE_BALANCE_* */
   gdouble awb_speed;
+  gint exposure;                /* GST_MI_EXPOSURE_* */
+  gdouble ae_target, ae_speed, ae_max_gain;
 } GstMiColourProps;
 
 /* the running state of white-balance=grey-world: the red and blue gain in use (gst_mi_awb_start / gst_mi_awb_step) */
@@ -57,6 +72,12 @@ typedef struct
 {
   gdouble gain[2];
 } GstMiAwb;
+
+/* the running state of exposure=auto: the factor on the three gains (1 to start with; gst_mi_auto_step) */
+typedef struct
+{
+  gdouble e;
+} GstMiAe;
 
 /* the ids an element's property enum reserves, in this order, from its `first` id on */
 enum
@@ -70,11 +91,35 @@ enum
   GST_MI_COLOUR_PROP_GAMMA,
   GST_MI_COLOUR_PROP_WHITE_BALANCE,
   GST_MI_COLOUR_PROP_AWB_SPEED,
+  GST_MI_COLOUR_PROP_EXPOSURE,
+  GST_MI_COLOUR_PROP_AE_TARGET,
+  GST_MI_COLOUR_PROP_AE_SPEED,
+  GST_MI_COLOUR_PROP_AE_MAX_GAIN,
   GST_MI_COLOUR_N_PROPS
 };
 
 #define GST_MI_COLOUR_DEFAULT_GAMMA 2.2
 #define GST_MI_COLOUR_DEFAULT_AWB_SPEED 0.25
+#define GST_MI_COLOUR_DEFAULT_AE_TARGET 0.9
+#define GST_MI_COLOUR_DEFAULT_AE_SPEED 0.25
+#define GST_MI_COLOUR_DEFAULT_AE_MAX_GAIN 4.0
+#define GST_MI_AE_FRACTION 0.99
+
+static GType
+gst_mi_colour_exposure_get_type (void)
+{
+  static gsize type = 0;
+  static const GEnumValue values[] = {
+    {GST_MI_EXPOSURE_MANUAL, "Manual: the gain properties as they are", "manual"},
+    {GST_MI_EXPOSURE_AUTO, "Auto: one factor on all gains follows the histogram of the frames", "auto"},
+    {0, NULL, NULL}
+  };
+  if (g_once_init_enter (&type)) {
+    GType t = g_enum_register_static (GST_MI_COLOUR_TONE_TYPE_NAME "Exposure", values);
+    g_once_init_leave (&type, t);
+  }
+  return (GType) type;
+}
 
 static GType
 gst_mi_colour_white_balance_get_type (void)
@@ -120,6 +165,10 @@ gst_mi_colour_props_init (GstMiColourProps * p)
   p->gamma = GST_MI_COLOUR_DEFAULT_GAMMA;
   p->white_balance = GST_MI_WHITE_BALANCE_MANUAL;
   p->awb_speed = GST_MI_COLOUR_DEFAULT_AWB_SPEED;
+  p->exposure = GST_MI_EXPOSURE_MANUAL;
+  p->ae_target = GST_MI_COLOUR_DEFAULT_AE_TARGET;
+  p->ae_speed = GST_MI_COLOUR_DEFAULT_AE_SPEED;
+  p->ae_max_gain = GST_MI_COLOUR_DEFAULT_AE_MAX_GAIN;
 }
 
 static void
@@ -139,13 +188,14 @@ gst_mi_colour_props_copy (GstMiColourProps * dst, const GstMiColourProps * src)
   dst->ccm = ccm;
 }
 
-/* gamma alone changes nothing: it is read by tone-curve=gamma only (and awb-speed by white-balance=grey-world) */
+/* gamma alone changes nothing: it is read by tone-curve=gamma only (and awb-speed by white-balance=grey-world, the
+ * ae-* properties by exposure=auto) */
 static gboolean
 gst_mi_colour_props_are_default (const GstMiColourProps * p)
 {
   return p->black_level == 0 && p->gain[0] == 1.0 && p->gain[1] == 1.0 && p->gain[2] == 1.0
       && (p->ccm == NULL || p->ccm[0] == '\0') && p->tone_curve == MIBAYER_TONE_LINEAR
-      && p->white_balance == GST_MI_WHITE_BALANCE_MANUAL;
+      && p->white_balance == GST_MI_WHITE_BALANCE_MANUAL && p->exposure == GST_MI_EXPOSURE_MANUAL;
 }
 
 /* The mibayer_colour of the properties, built with the library's helpers so that everybody rounds alike.  FALSE with a
@@ -239,6 +289,56 @@ gst_mi_awb_step (const GstMiColourProps * p, GstMiAwb * awb, const mibayer_stats
   return TRUE;
 }
 
+/* One step of the loops of an element with exposure=auto, on what it measured of a frame: `zone` (NULL unless
+ * white-balance=grey-world is on as well: that step runs first, as in gst_mi_awb_step, and its gains are the current
+ * ones) and the whole-frame histogram `hist`.  x = mibayer_hist_exposure (hist, black-level, the current gains before
+ * e, 0.99, ae-target, ae-max-gain); e += ae-speed x (x - e); the stage gets gain_k x e, clamped to the gain range.  TRUE
+ * with the stage to use from now on in `out`; FALSE when nothing changes (neither helper had an answer, or the new matrix
+ * would leave its range). */
+static G_GNUC_UNUSED gboolean
+gst_mi_auto_step (const GstMiColourProps * p, GstMiAwb * awb, GstMiAe * ae, const mibayer_stats_zone * zone,
+    const mibayer_hist * hist, gint pattern, gint depth, mibayer_colour * out)
+{
+  const double black[3] = { p->black_level, p->black_level, p->black_level };
+  double gw[3], x, e = ae->e;
+  GstMiColourProps q = *p, r;   /* share the ccm string: not cleared */
+  gboolean moved = FALSE;
+  gchar *why = NULL;
+  gint k;
+
+  if (p->white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD) {
+    q.gain[0] = awb->gain[0];
+    q.gain[2] = awb->gain[1];
+    if (zone && mibayer_stats_grey_world && mibayer_stats_grey_world (zone, 1, pattern, black, gw) == 1) {
+      for (k = 0; k < 2; k++) {
+        const gdouble g = awb->gain[k] + p->awb_speed * (p->gain[1] * gw[2 * k] - awb->gain[k]);
+        q.gain[2 * k] = CLAMP (g, 0.0, 15.99);
+      }
+      moved = TRUE;
+    }
+  }
+  if (hist && mibayer_hist_exposure && mibayer_hist_exposure (hist, pattern, depth, black, q.gain, GST_MI_AE_FRACTION,
+          p->ae_target, p->ae_max_gain, &x) == 1) {
+    e += p->ae_speed * (x - e);
+    moved = TRUE;
+  }
+  if (!moved)
+    return FALSE;
+  r = q;
+  for (k = 0; k < 3; k++) {
+    const gdouble g = q.gain[k] * e;
+    r.gain[k] = CLAMP (g, 0.0, 15.99);
+  }
+  if (!gst_mi_colour_props_build (&r, out, &why)) {
+    g_free (why);
+    return FALSE;
+  }
+  awb->gain[0] = q.gain[0];
+  awb->gain[1] = q.gain[2];
+  ae->e = e;
+  return TRUE;
+}
+
 static void
 gst_mi_colour_install_properties (GObjectClass * object_class, guint first)
 {
@@ -279,6 +379,24 @@ gst_mi_colour_install_properties (GObjectClass * object_class, guint first)
       g_param_spec_double ("awb-speed", "AWB speed",
           "white-balance=grey-world: gain += awb-speed x (target - gain) after every frame; 1 = jump",
           G_MINDOUBLE, 1.0, GST_MI_COLOUR_DEFAULT_AWB_SPEED, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_EXPOSURE,
+      g_param_spec_enum ("exposure", "Exposure",
+          "manual: the gain properties as they are; auto: turns the colour stage on, reads the mosaic "
+          "histogram of every frame and moves one factor on all three gains so that the 99th percentile "
+          "of the brightest channel lands on ae-target, for the frames accepted afterwards",
+          gst_mi_colour_exposure_get_type (), GST_MI_EXPOSURE_MANUAL, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_AE_TARGET,
+      g_param_spec_double ("ae-target", "AE target",
+          "exposure=auto: where the 99th percentile should sit, as a fraction of full scale",
+          G_MINDOUBLE, 1.0, GST_MI_COLOUR_DEFAULT_AE_TARGET, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_AE_SPEED,
+      g_param_spec_double ("ae-speed", "AE speed",
+          "exposure=auto: factor += ae-speed x (wanted - factor) after every frame; 1 = jump",
+          G_MINDOUBLE, 1.0, GST_MI_COLOUR_DEFAULT_AE_SPEED, flags));
+  g_object_class_install_property (object_class, first + GST_MI_COLOUR_PROP_AE_MAX_GAIN,
+      g_param_spec_double ("ae-max-gain", "AE maximum gain",
+          "exposure=auto: the largest factor the loop asks for", 1.0, 15.99,
+          GST_MI_COLOUR_DEFAULT_AE_MAX_GAIN, flags));
 }
 
 /* TRUE when `id` (relative to the element's first colour id) is a colour property; the caller holds its lock */
@@ -309,6 +427,18 @@ gst_mi_colour_set_property (GstMiColourProps * p, gint id, const GValue * value)
       return TRUE;
     case GST_MI_COLOUR_PROP_AWB_SPEED:
       p->awb_speed = g_value_get_double (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_EXPOSURE:
+      p->exposure = g_value_get_enum (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_TARGET:
+      p->ae_target = g_value_get_double (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_SPEED:
+      p->ae_speed = g_value_get_double (value);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_MAX_GAIN:
+      p->ae_max_gain = g_value_get_double (value);
       return TRUE;
     default:
       return FALSE;
@@ -341,6 +471,18 @@ gst_mi_colour_get_property (const GstMiColourProps * p, gint id, GValue * value)
       return TRUE;
     case GST_MI_COLOUR_PROP_AWB_SPEED:
       g_value_set_double (value, p->awb_speed);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_EXPOSURE:
+      g_value_set_enum (value, p->exposure);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_TARGET:
+      g_value_set_double (value, p->ae_target);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_SPEED:
+      g_value_set_double (value, p->ae_speed);
+      return TRUE;
+    case GST_MI_COLOUR_PROP_AE_MAX_GAIN:
+      g_value_set_double (value, p->ae_max_gain);
       return TRUE;
     default:
       return FALSE;

@@ -836,6 +836,10 @@ typedef struct
   guint32 awb_lo, awb_hi;
   gpointer awb_d, awb_h, awb_ev;
   gboolean awb_pending;
+  /* exposure=auto: the factor in use; its histogram rides behind the zone in awb_d / awb_h, under the same event and the
+   * same one-measurement-in-flight rule (awb_props then holds the latched properties, grey-world or not) */
+  gboolean ae_on;
+  GstMiAe ae;
   gboolean prerolled;           /* a frame has left since start / flush: batching may begin */
   GQueue waiting;               /* Hb2rPair* */
   GQueue ready;                 /* GstBuffer* */
@@ -893,6 +897,10 @@ G_DEFINE_TYPE (GstMiHipBayer2RGB, gst_mi_hip_bayer2rgb, GST_TYPE_BASE_TRANSFORM)
     "{ RGBx, xRGB, BGRx, xBGR, RGBA, ARGB, BGRA, ABGR }") "; " \
     GST_VIDEO_CAPS_MAKE_WITH_FEATURES (GST_CAPS_FEATURE_MEMORY_HIP, "{ RGB, BGR }")
 
+/* the measurement buffer of the two loops: one zone, then one histogram */
+#define HB2R_AUTO_BYTES (sizeof (mibayer_stats_zone) + sizeof (mibayer_hist))
+#define HB2R_AE_HIST(base) ((mibayer_hist *) ((guint8 *) (base) + sizeof (mibayer_stats_zone)))
+
 /* white-balance=grey-world: the measurement and its state go with the context (whose device they live on) */
 static void
 hb2r_awb_drop (GstMiHipBayer2RGB * self)
@@ -907,7 +915,7 @@ hb2r_awb_drop (GstMiHipBayer2RGB * self)
   if (self->awb_h)
     mibayer_host_free (self->awb_h);
   self->awb_ev = self->awb_d = self->awb_h = NULL;
-  self->awb_pending = self->awb_on = FALSE;
+  self->awb_pending = self->awb_on = self->ae_on = FALSE;
   gst_mi_colour_props_clear (&self->awb_props);
 }
 
@@ -920,7 +928,11 @@ hb2r_awb_poll (GstMiHipBayer2RGB * self)
   if (!self->awb_pending || mibayer_dev_event_query (self->ctx_device, self->awb_ev) == 0)
     return;
   self->awb_pending = FALSE;
-  if (gst_mi_awb_step (&self->awb_props, &self->awb, (const mibayer_stats_zone *) self->awb_h, self->format, &colour))
+  if (self->ae_on
+      ? gst_mi_auto_step (&self->awb_props, &self->awb, &self->ae,
+          self->awb_on ? (const mibayer_stats_zone *) self->awb_h : NULL, HB2R_AE_HIST (self->awb_h), self->format, 8,
+          &colour)
+      : gst_mi_awb_step (&self->awb_props, &self->awb, (const mibayer_stats_zone *) self->awb_h, self->format, &colour))
     (void) mibayer_set_colour (self->ctx, &colour);
 }
 
@@ -929,12 +941,13 @@ hb2r_awb_poll (GstMiHipBayer2RGB * self)
 static void
 hb2r_awb_measure (GstMiHipBayer2RGB * self, const void *d_src, gpointer stream)
 {
-  if (!self->awb_on || self->awb_pending)
+  if ((!self->awb_on && !self->ae_on) || self->awb_pending)
     return;
-  if (mibayer_stats_device (self->ctx, d_src, 0, 1, 1, 1, self->awb_lo, self->awb_hi,
-          (mibayer_stats_zone *) self->awb_d, stream) == MIBAYER_OK
-      && mibayer_dev_download_async (self->ctx_device, self->awb_h, self->awb_d, sizeof (mibayer_stats_zone),
-          stream) == MIBAYER_OK
+  if ((!self->awb_on || mibayer_stats_device (self->ctx, d_src, 0, 1, 1, 1, self->awb_lo, self->awb_hi,
+              (mibayer_stats_zone *) self->awb_d, stream) == MIBAYER_OK)
+      && (!self->ae_on || mibayer_hist_device (self->ctx, d_src, 0, 1, 0, 0, 0, 0, HB2R_AE_HIST (self->awb_d),
+              stream) == MIBAYER_OK)
+      && mibayer_dev_download_async (self->ctx_device, self->awb_h, self->awb_d, HB2R_AUTO_BYTES, stream) == MIBAYER_OK
       && mibayer_dev_event_record (self->ctx_device, self->awb_ev, stream) == MIBAYER_OK)
     self->awb_pending = TRUE;
 }
@@ -1215,7 +1228,7 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
 {
   mibayer_cfg cfg;
   mibayer_colour colour;
-  gboolean want_colour = FALSE, want_awb = FALSE;
+  gboolean want_colour = FALSE, want_awb = FALSE, want_ae = FALSE;
   int rc;
 
   if (self->ctx != NULL && self->ctx_device == device)
@@ -1230,11 +1243,17 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
     if (want_colour)
       ok = gst_mi_colour_props_build (&self->colour, &colour, &why) && mibayer_set_colour != NULL;
     want_awb = ok && want_colour && self->colour.white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD;
-    if (want_awb) {
+    want_ae = ok && want_colour && self->colour.exposure == GST_MI_EXPOSURE_AUTO;
+    if (want_awb || want_ae) {
       gst_mi_colour_props_copy (&self->awb_props, &self->colour);
       gst_mi_awb_start (&self->awb_props, &self->awb, 8, &self->awb_lo, &self->awb_hi);
+      self->ae.e = 1.0;
     }
     GST_OBJECT_UNLOCK (self);
+    if (want_ae && (!mibayer_hist_device || !mibayer_hist_exposure)) {
+      ok = FALSE;
+      why = g_strdup ("exposure=auto: this libmibayer has no mosaic histogram");
+    }
     if (want_awb && (!mibayer_stats_device || !mibayer_stats_grey_world)) {
       ok = FALSE;
       why = g_strdup ("white-balance=grey-world: this libmibayer has no mosaic statistics");
@@ -1283,18 +1302,19 @@ hb2r_ensure_ctx (GstMiHipBayer2RGB * self, gint device)
     return FALSE;
   }
   self->ctx_device = device;
-  if (want_awb) {
-    self->awb_d = mibayer_dev_alloc (device, sizeof (mibayer_stats_zone));
-    self->awb_h = mibayer_host_alloc (sizeof (mibayer_stats_zone));
+  if (want_awb || want_ae) {
+    self->awb_d = mibayer_dev_alloc (device, HB2R_AUTO_BYTES);
+    self->awb_h = mibayer_host_alloc (HB2R_AUTO_BYTES);
     self->awb_ev = mibayer_dev_event_create (device);
     if (!self->awb_d || !self->awb_h || !self->awb_ev) {
       hb2r_drop_ctx (self);
       GST_ELEMENT_ERROR (self, RESOURCE, FAILED,
-          ("%s: cannot set up white-balance=grey-world", HB2R_LABEL (self)),
-          ("no memory for the statistics zone: %s", mibayer_last_hip_error ()));
+          ("%s: cannot set up white-balance=grey-world / exposure=auto", HB2R_LABEL (self)),
+          ("no memory for the measurement: %s", mibayer_last_hip_error ()));
       return FALSE;
     }
-    self->awb_on = TRUE;
+    self->awb_on = want_awb;
+    self->ae_on = want_ae;
   }
   self->tl_stream = mibayer_ctx_stream (self->ctx);
   self->tl = gst_mi_hip_timeline_for (device, self->tl_stream);

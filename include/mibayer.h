@@ -67,6 +67,7 @@ extern "C" {
 /* 5, later additive: the fused colour stage -- MIBAYER_FLAG_COLOUR, struct mibayer_colour and the entry points of
  * group `colour`; a cfg without the flag means what it meant. */
 /* 5, later additive: mosaic zone statistics -- struct mibayer_stats_zone and the entry points of group `stats`. */
+/* 5, later additive: mosaic histogram -- struct mibayer_hist and the entry points of group `hist`. */
 /* 5, later additive: packed 24-bit output -- MIBAYER_FLAG_DST_24BIT, a fifth deep flag; no struct field and no entry
  * point was added, and a cfg without the flag means what it meant. */
 /* 5, later additive: planar 8-bit output -- MIBAYER_FLAG_DST_PLANAR, a sixth deep flag; no struct field and no entry
@@ -105,6 +106,10 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group hist: the other half of the ISP statistics block -- a 256-bin histogram per CFA site of the mosaic, and the
+ *   percentile and auto-exposure helpers that read it
+ *     mibayer_hist_device mibayer_set_hist mibayer_frame_hist mibayer_pool_set_hist mibayer_pool_frame_hist
+ *     mibayer_hist_percentile mibayer_hist_exposure
  * group stats: the ISP statistics block -- per-zone sums and counts per CFA site of the mosaic, and grey-world white balance
  *     mibayer_stats_device mibayer_set_stats mibayer_frame_stats mibayer_pool_set_stats mibayer_pool_frame_stats
  *     mibayer_stats_grey_world
@@ -399,6 +404,55 @@ int mibayer_pool_frame_stats (mibayer_pool *pool, mibayer_stats_zone *out, int n
  * NULL pointer, nzones < 1 or a pattern that is no mibayer_pattern. */
 int mibayer_stats_grey_world (const mibayer_stats_zone *zones, int nzones, int pattern, const double black[3],
     double gains[3]);
+
+/* ---- mosaic histogram (additive within version 5: a struct and the entry points of group `hist`) --------------- */
+
+/* What auto exposure, auto levels and a clipping warning read: 256 bins per CFA site over a window of the MOSAIC, by a
+ * read-only kernel.  Sample S, depth and site s as in group `stats` above.
+ *   bin      S >> (depth - 8)
+ *   window   (x0, y0, w, h): x0 and w even, w >= 2, h >= 1, x0 >= 0, y0 >= 0, x0 + w <= W, y0 + h <= H; (0, 0, 0, 0) is
+ *            the whole frame, the last row of an odd height included.  Anything else: MIBAYER_ERR_ARG.  A window with
+ *            more than 2^32 - 1 samples on one site: MIBAYER_ERR_GEOMETRY.
+ * bin[s][b] = the number of samples of site s inside the window whose bin is b.  Columns >= W, stride padding and the
+ * bits above `bits` never count.  Integers only: the result does not depend on the order of the kernel's atomics. */
+#define MIBAYER_HIST_BINS 256
+typedef struct mibayer_hist {           /* 4096 bytes */
+  uint32_t bin[4][MIBAYER_HIST_BINS];   /* [site][bin] */
+} mibayer_hist;
+
+/* Device path: zeroes d_hist (nframes histograms, frame-major) on `hip_stream`, then ONE launch over the batch, frame f
+ * read at d_src + f * src_frame_bytes as by mibayer_process_device.  Valid on every bayer2rgb context (8-bit, deep, MHC,
+ * COLOUR, 24-bit, planar).  MIBAYER_ERR_ARG on an RGB2BAYER context, a window outside the rule above, d_src or d_hist not
+ * a multiple of 4, nframes < 0; MIBAYER_ERR_GEOMETRY for a frame pitch as in mibayer_process_device.  Covered by
+ * mibayer_sync when launched on the context's stream. */
+int mibayer_hist_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, int nframes, int x0, int y0,
+    int w, int h, mibayer_hist *d_hist, void *hip_stream);
+/* Host path, as mibayer_set_stats / mibayer_frame_stats in every respect: on != 0, every frame accepted after this
+ * returns also gets the histogram of that window, computed once on the slot's device copy of the mosaic behind the
+ * (last band's) demosaic launch and downloaded with the frame into pinned memory of the slot; on = 0 switches it off
+ * again (the default; the window is then ignored).  The converted bytes are the same with and without, a
+ * MIBAYER_FLAG_HIPGRAPH context launches without graphs meanwhile, and statistics may be on as well.
+ * mibayer_frame_hist: the histogram of the frame handed back last; MIBAYER_ERR_EMPTY before the first frame or when that
+ * frame was accepted with histograms off. */
+int mibayer_set_hist (mibayer_ctx *ctx, int on, int x0, int y0, int w, int h);
+int mibayer_frame_hist (mibayer_ctx *ctx, mibayer_hist *out);
+/* ... of a pool: window and histogram are kept with each frame like the zones; a frame redone on another shard brings
+ * its own, a frame returned as lost has none (MIBAYER_ERR_EMPTY). */
+int mibayer_pool_set_hist (mibayer_pool *pool, int on, int x0, int y0, int w, int h);
+int mibayer_pool_frame_hist (mibayer_pool *pool, mibayer_hist *out);
+/* Percentile bin (pure host code, no device).  colour 0 / 1 / 2 = R / G / B (both green sites pooled into G), 3 = all
+ * four sites pooled; N = the pooled count.  N == 0: *bin = -1, returns 0.  Else rank r = max (1, (uint64) ceil (fraction
+ * * (double) N)), *bin = the smallest b whose inclusive cumulative count is >= r, returns 1.  MIBAYER_ERR_ARG for a NULL
+ * pointer, a pattern that is no mibayer_pattern, a colour outside 0 .. 3 or a fraction outside [0, 1] (NaN included). */
+int mibayer_hist_percentile (const mibayer_hist *hist, int pattern, int colour, double fraction, int *bin);
+/* Exposure factor from a histogram (pure host code, doubles, in exactly this order).  max = 2^depth - 1.  Per colour k:
+ * b_k = its percentile bin at `fraction`, v_k = (b_k + 1) * 2^(depth - 8) - 1 (the top of that bin at native depth),
+ * level_k = gains[k] * fmax (v_k - black[k], 0) / (max - black[k]); level = max_k level_k.  A colour without samples,
+ * black[k] >= max or level <= 0: *exposure = 1, returns 0.  Else *exposure = clamp (target / level, 1/16, max_gain),
+ * returns 1.  black NULL = 0, gains NULL = (1, 1, 1).  MIBAYER_ERR_ARG for a NULL hist or exposure, a bad pattern or
+ * fraction, depth outside {8, 10, 12, 14, 16}, target outside (0, 1] or max_gain outside [1, 15.99]. */
+int mibayer_hist_exposure (const mibayer_hist *hist, int pattern, int depth, const double black[3],
+    const double gains[3], double fraction, double target, double max_gain, double *exposure);
 
 /* ---- global ------------------------------------------------------------- */
 

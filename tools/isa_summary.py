@@ -49,11 +49,14 @@ PRODUCTION = tile_kernels() + [
     ("Malvar-He-Cutler: 16-bit words -> 8-bit channels", "bayer2rgb_mhc_kernelILb0ELb0EE"),
     ("Malvar-He-Cutler: 16-bit words -> 16-bit channels", "bayer2rgb_mhc_kernelILb0ELb1EE"),
     ("fused colour stage: either demosaic, every sample / channel width (run-time branches)", "bayer2rgb_colour_kernel"),
+    ("mosaic zone statistics: both sample widths and byte orders (run-time branches)", "mosaic_stats_kernel"),
+    ("mosaic histogram: both sample widths and byte orders (run-time branches)", "mosaic_hist_kernel"),
 ]
 INTERESTING = ["v_lerp_u8", "v_perm_b32", "v_alignbit_b32", "v_bfi_b32", "v_mov_b32_dpp", "ds_bpermute_b32",
                "global_load_dwordx4", "global_load_dwordx2", "global_load_dword", "global_store_dwordx4",
                "global_store_dwordx3", "global_store_dwordx2", "global_store_dword", "global_store_short",
-               "ds_write_b128", "ds_write_b32", "ds_read_b32",
+               "ds_write_b128", "ds_write_b32", "ds_read_b32", "ds_add_u32", "ds_add_u64", "global_atomic_add",
+               "global_atomic_add_x2",
                "ds_read_b128", "ds_read2_b32", "v_mad_i32_i24", "v_mad_u32_u24", "v_mul_i32_i24", "v_mul_u32_u24", "s_sleep", "s_barrier", "s_waitcnt", "v_mfma", "scratch_", "buffer_"]
 
 subprocess.run(["make", "-C", PKG, "asm"], check=True, stdout=subprocess.DEVNULL)
