@@ -762,6 +762,27 @@ static void plan_selectors (const mibayer_cfg &f, uint32_t sel[4],
   }
 }
 
+/* the mosaic's samples as the strip, statistics and histogram kernels take them */
+struct SampleFormat {
+  int bits;                     /* significant bits; 8: an 8-bit mosaic */
+  bool in8;                     /* four samples per dword, else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a source dword: identity or a byte swap per 16-bit word */
+  uint32_t vmax;                /* 2^bits - 1 */
+  uint32_t mask2;               /* ... in both halves of a dword */
+};
+
+static SampleFormat sample_format (const mibayer_cfg &f)
+{
+  SampleFormat sf;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  sf.bits = bits ? bits : 8;
+  sf.in8 = bits == 0;
+  sf.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
+  sf.vmax = (1u << sf.bits) - 1u;
+  sf.mask2 = sf.vmax * 0x00010001u;
+  return sf;
+}
+
 static void make_plan (mibayer_ctx *c)
 {
   plan_selectors (c->cfg, c->sel, c->swap_rows);
@@ -815,9 +836,9 @@ static void make_cgd_selectors (mibayer_ctx *c, int depth)
 static void make_deep_plan (mibayer_ctx *c)
 {
   const mibayer_cfg &f = c->cfg;
-  const uint32_t bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
-  const int depth = bits ? (int) bits : 8;
-  c->kind.in8 = bits == 0;
+  const SampleFormat sf = sample_format (f);
+  const int depth = sf.bits;
+  c->kind.in8 = sf.in8;
   c->kind.out16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
   DeepParams &q = c->deep_args;
   q = DeepParams ();
@@ -827,8 +848,8 @@ static void make_deep_plan (mibayer_ctx *c)
   q.dst_stride = f.dst_stride;
   q.dn_last = f.height >= 4 ? f.height - 4 : 1;        /* gstbayer2rgb.c:430-447 */
   q.swap_rows = c->swap_rows;
-  q.in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
-  q.mask2 = depth >= 16 ? 0xffffffffu : ((1u << depth) - 1u) * 0x00010001u;
+  q.in_sel = sf.in_sel;
+  q.mask2 = sf.mask2;
   q.out_shift = c->kind.out16 ? 16 - depth : depth - 8;
   q.px3 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
   if (f.flags & MIBAYER_FLAG_DST_PLANAR) {
@@ -898,9 +919,63 @@ static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes,
   return MIBAYER_OK;
 }
 
-static bool aligned16 (const void *p)
+/* The frames of one launch (host side only, never part of a kernel argument): a strided batch, frame f at src / dst +
+ * f * frame bytes, or a list of n <= kMaxList separate allocations.  Every launch description asks its alignment
+ * questions here. */
+struct FrameSet {
+  const uint8_t *src;
+  uint8_t *dst;
+  size_t src_frame_bytes, dst_frame_bytes;
+  const void *const *srcs;              /* the list form */
+  void *const *dsts;
+  int n;                                /* frames */
+
+  static FrameSet strided (const void *src, size_t src_frame_bytes, void *dst, size_t dst_frame_bytes, int nframes)
+  {
+    return { (const uint8_t *) src, (uint8_t *) dst, src_frame_bytes, dst_frame_bytes, nullptr, nullptr, nframes };
+  }
+  static FrameSet list (const void *const *srcs, void *const *dsts, int n)
+  {
+    return { nullptr, nullptr, 0, 0, srcs, dsts, n };
+  }
+  bool is_list () const { return srcs != nullptr; }
+  /* every frame of `list`, or of the batch at `base` (the stride of a single frame does not count), starts on an
+   * a-byte grid; a is a power of two */
+  template <typename T>
+  bool on_grid (T *const *list, const void *base, size_t frame_bytes, unsigned a) const
+  {
+    if (!list)
+      return (((uintptr_t) base) & (a - 1)) == 0 && (n == 1 || frame_bytes % a == 0);
+    for (int f = 0; f < n; f++)
+      if (((uintptr_t) list[f]) & (a - 1))
+        return false;
+    return true;
+  }
+  bool srcs16 () const { return on_grid (srcs, src, src_frame_bytes, 16); }
+  bool all16 () const { return srcs16 () && on_grid (dsts, dst, dst_frame_bytes, 16); }
+  bool dsts8 () const { return on_grid (dsts, dst, dst_frame_bytes, 8); }
+  /* the destination rows can sit on an a-byte grid; never said of a list */
+  bool dst_on_grid (unsigned a) const { return !is_list () && on_grid (dsts, dst, dst_frame_bytes, a); }
+  /* the frame part of a kernel's arguments (KParams, DeepParams, R2BParams) */
+  template <typename P>
+  void fill (P &p) const
+  {
+    p.src = src;
+    p.dst = dst;
+    p.src_frame_bytes = src_frame_bytes;
+    p.dst_frame_bytes = dst_frame_bytes;
+    p.nlist = is_list () ? n : 0;
+    for (int f = 0; f < p.nlist; f++) {
+      p.src_list[f] = (const uint8_t *) srcs[f];
+      p.dst_list[f] = (uint8_t *) dsts[f];
+    }
+  }
+};
+
+/* the frame of a host-path slot on the device */
+static FrameSet slot_frame (const mibayer_ctx *c, const Slot &s)
 {
-  return (((uintptr_t) p) & 15u) == 0;
+  return FrameSet::strided (s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1);
 }
 
 /* Launches of at most this many rounds of workgroups take the PLAN_FRAME plan (a production workgroup covers 8192
@@ -930,16 +1005,21 @@ struct Geometry {
   const Variant *var;           /* the shape the launch class of this launch runs in */
 };
 
-static void fill_params (const mibayer_ctx *c, const Plan &pl, KParams &p, Geometry &g,
-    const void *d_src, size_t src_frame_bytes, void *d_dst,
-    size_t dst_frame_bytes, int nframes)
+typedef void (*KernelFn) (KParams);
+
+/* one launch of a tile kernel: its arguments, which kernel (16-byte fast path, generic or sector-aligned arm), grid */
+struct TileLaunch {
+  KParams p;
+  KernelFn kern;
+  unsigned grid, threads;
+  Geometry g;
+};
+
+static void fill_params (const mibayer_ctx *c, const Plan &pl, KParams &p, Geometry &g, const FrameSet &fs)
 {
   const mibayer_cfg &f = c->cfg;
   g.var = pl.var;
-  p.src = (const uint8_t *) d_src;
-  p.dst = (uint8_t *) d_dst;
-  p.src_frame_bytes = src_frame_bytes;
-  p.dst_frame_bytes = dst_frame_bytes;
+  fs.fill (p);
   p.width = f.width;
   p.height = f.height;
   p.src_stride = f.src_stride;
@@ -948,7 +1028,7 @@ static void fill_params (const mibayer_ctx *c, const Plan &pl, KParams &p, Geome
   p.dn_last = f.height >= 4 ? f.height - 4 : 1;   /* ring slot reuse, :430-447 */
   g.tiles_x = (f.width + pl.var->tile_w - 1) / pl.var->tile_w;
   g.tiles_y = (f.height + pl.var->tile_h - 1) / pl.var->tile_h;
-  g.tile_rows = (long long) nframes * g.tiles_y;
+  g.tile_rows = (long long) fs.n * g.tiles_y;
   int band = pl.band != INT32_MIN ? pl.band : pl.var->band;
   if (band < 0)                 /* one contiguous chunk of tile rows per XCD */
     band = (int) ((g.tile_rows + kNumXcd - 1) / kNumXcd);
@@ -957,24 +1037,20 @@ static void fill_params (const mibayer_ctx *c, const Plan &pl, KParams &p, Geome
     p.sel[k] = c->sel[k];
   p.swap_rows = c->swap_rows;
   p.start_sleep = c->start_sleep > 0 ? c->start_sleep : 0;      /* auto: plan_launch */
-  p.nlist = 0;
 }
-
-typedef void (*KernelFn) (KParams);
 
 constexpr int kStartSleepChunk = 24;    /* x s_sleep(1) = 64 clocks each */
 
-/* everything a launch needs: arguments, kernel (16-byte fast path or generic),
- * grid size */
-static int plan_launch (const mibayer_ctx *c, const void *d_src,
-    size_t src_frame_bytes, void *d_dst, size_t dst_frame_bytes, int nframes,
-    KParams &p, KernelFn &kern, unsigned &grid, Geometry *geom = nullptr,
-    long long tile_row0 = 0, long long ntile_rows = -1, int pointers_aligned16 = -1)
+/* everything a launch of the context's tile kernel over `fs` needs (a list is planned as a batch of fs.n frames):
+ * all its tile rows, or [tile_row0, tile_row0 + ntile_rows) of them */
+static int plan_launch (const mibayer_ctx *c, const FrameSet &fs, TileLaunch &t,
+    long long tile_row0 = 0, long long ntile_rows = -1)
 {
-  Geometry g;
-  const Plan &pl = plan_for (c, nframes);
-  fill_params (c, pl, p, g, d_src, src_frame_bytes, d_dst, dst_frame_bytes,
-      nframes);
+  KParams &p = t.p;
+  Geometry &g = t.g;
+  const Plan &pl = plan_for (c, fs.n);
+  fill_params (c, pl, p, g, fs);
+  t.threads = (unsigned) pl.var->threads;
   if (ntile_rows >= 0) {        /* one horizontal band of the batch */
     if (tile_row0 < 0 || tile_row0 + ntile_rows > g.tile_rows)
       return MIBAYER_ERR_ARG;
@@ -987,26 +1063,17 @@ static int plan_launch (const mibayer_ctx *c, const void *d_src,
   if (g.tile_rows * g.tiles_x > 0x7fffffffLL)
     return MIBAYER_ERR_GEOMETRY;
   const mibayer_cfg &f = c->cfg;
-  /* pointers_aligned16 >= 0: a list launch, whose caller has looked at every
-   * frame pointer itself (frame strides do not apply): 1 = all 16-byte aligned,
-   * 2 = every destination 8-byte aligned, 0 = neither */
   static const bool force_generic = LAB_GETENV ("MIBAYER_FORCE_GENERIC") != NULL;   /* A/B: tools/sweep2.py */
   const bool fast = !force_generic && (f.width % 16 == 0) && (f.src_stride % 16 == 0)
-      && (f.dst_stride % 16 == 0)
-      && (pointers_aligned16 >= 0 ? pointers_aligned16 == 1
-          : (aligned16 (d_src) && aligned16 (d_dst)
-              && (nframes == 1 || (src_frame_bytes % 16 == 0
-                      && dst_frame_bytes % 16 == 0))));
+      && (f.dst_stride % 16 == 0) && fs.all16 ();
+  KernelFn &kern = t.kern;
+  unsigned &grid = t.grid;
   kern = fast ? pl.var->fast : pl.var->generic;
   if (!fast && pl.align && (pl.align == 128 ? pl.var->aligned128 : pl.var->aligned64)) {
     /* output rows off the sector grid, all of them 8-byte aligned (even per-row shifts): the sector-aligned arm */
-    const bool rows8 = (f.dst_stride % 8 == 0)
-        && (pointers_aligned16 >= 0 ? pointers_aligned16 >= 1
-            : ((((uintptr_t) d_dst) & 7u) == 0 && (nframes == 1 || dst_frame_bytes % 8 == 0)));
+    const bool rows8 = (f.dst_stride % 8 == 0) && fs.dsts8 ();
     const unsigned a = (unsigned) pl.align;
-    const bool on_grid = (f.dst_stride % a == 0)
-        && (pointers_aligned16 >= 0 ? false
-            : ((((uintptr_t) d_dst) & (a - 1)) == 0 && (nframes == 1 || dst_frame_bytes % a == 0)));
+    const bool on_grid = (f.dst_stride % a == 0) && fs.dst_on_grid (a);
     static const bool force_arm = LAB_GETENV ("MIBAYER_FORCE_ALIGNED_ARM") != NULL;     /* A/B: tools/sweep2.py */
     if (rows8 && (!on_grid || force_arm))
       kern = pl.align == 128 ? pl.var->aligned128 : pl.var->aligned64;
@@ -1051,60 +1118,86 @@ static int plan_launch (const mibayer_ctx *c, const void *d_src,
   if (c->start_sleep < 0)
     p.start_sleep = (g.band > 0 && !pl.var->persistent
         && (long long) grid > 16LL * c->num_cus) ? kStartSleepChunk : 0;
-  if (geom)
-    *geom = g;
   return MIBAYER_OK;
 }
 
-static int launch (const mibayer_ctx *c, const void *d_src,
-    size_t src_frame_bytes, void *d_dst, size_t dst_frame_bytes, int nframes,
-    hipStream_t stream, long long tile_row0 = 0, long long ntile_rows = -1, const ColourStage *stage = nullptr)
+/* the tile launch as the kernel node of a graph; `args` has to live until the node has been added */
+static hipKernelNodeParams kernel_node_params (TileLaunch &t, void *args[1])
 {
-  if (nframes == 0 || ntile_rows == 0)
+  hipKernelNodeParams kp;
+  memset (&kp, 0, sizeof kp);
+  args[0] = &t.p;
+  kp.func = (void *) t.kern;
+  kp.gridDim = dim3 (t.grid);
+  kp.blockDim = dim3 (t.threads);
+  kp.kernelParams = args;
+  return kp;
+}
+
+/* the arguments of the context's rgb2bayer kernels that do not depend on the frames */
+static void r2b_params (const mibayer_ctx *c, R2BParams &q)
+{
+  const mibayer_cfg &f = c->cfg;
+  q.width = f.width;
+  q.height = f.height;
+  q.src_stride = f.src_stride;
+  q.dst_stride = f.dst_stride;
+  q.out_dwords = ((f.width + 3) & ~3) / 4;
+  /* block order: identity for the flat kernel (82.5 % of peak against 77.5 % with one chunk of
+   * the batch per XCD), one chunk per XCD for the tile kernel (74.4 vs 73.8 %) --
+   * profiles/r02_rgb2bayer_sweep.log */
+  q.band = c->plan[PLAN_BATCH].band != INT32_MIN ? c->plan[PLAN_BATCH].band
+      : (c->r2b_flat_k > 0 ? 0 : -1);
+  q.start_sleep = c->start_sleep > 0 ? c->start_sleep : 0;
+  q.flat_k = c->r2b_flat_k;
+  q.flat_px = c->r2b_flat_px;
+  q.flat_ld = c->r2b_flat_ld;
+  q.rows = c->r2b_rows;
+  for (int k = 0; k < 2; k++) {
+    q.sel_lo[k] = c->r2b_lo[k];
+    q.sel_hi[k] = c->r2b_hi[k];
+  }
+}
+
+/* One launch of the context's kernel over the frames of `fs`: all of them, or units [row0, row0 + nrows) of the batch
+ * (host-path bands; a unit is a tile row, a chunk of kStripRows rows or kInverseBandUnit rows, by kernel family).
+ * stage: the colour stage to launch with (a colour context); NULL = the context's current one */
+static int launch_frames (const mibayer_ctx *c, const FrameSet &fs, hipStream_t stream, long long row0 = 0,
+    long long nrows = -1, const ColourStage *stage = nullptr)
+{
+  if (fs.n == 0 || nrows == 0)
     return MIBAYER_OK;
-  if (c->deep) {                /* tile rows = chunks of kStripRows rows */
+  if (nrows < 0)
+    row0 = 0;
+  if (c->deep) {
     DeepParams q = c->deep_args;
-    q.src = (const uint8_t *) d_src;
-    q.dst = (uint8_t *) d_dst;
-    q.src_frame_bytes = src_frame_bytes;
-    q.dst_frame_bytes = dst_frame_bytes;
-    q.nlist = 0;
-    return ntile_rows >= 0 ? launch_deep_kernel (c, q, nframes, stream, tile_row0, ntile_rows, stage)
-        : launch_deep_kernel (c, q, nframes, stream, 0, -1, stage);
+    fs.fill (q);
+    return launch_deep_kernel (c, q, fs.n, stream, row0, nrows, stage);
   }
   if (c->inverse) {
     const mibayer_cfg &f = c->cfg;
-    R2BParams q;
-    q.src = (const uint8_t *) d_src;
-    q.dst = (uint8_t *) d_dst;
-    q.src_frame_bytes = src_frame_bytes;
-    q.dst_frame_bytes = dst_frame_bytes;
-    q.width = f.width;
-    q.height = f.height;
-    q.src_stride = f.src_stride;
-    q.dst_stride = f.dst_stride;
-    q.out_dwords = ((f.width + 3) & ~3) / 4;
-    q.total_rows = (long long) nframes * f.height;
-    /* block order: identity for the flat kernel (82.5 % of peak against 77.5 % with one chunk of
-     * the batch per XCD), one chunk per XCD for the tile kernel (74.4 vs 73.8 %) --
-     * profiles/r02_rgb2bayer_sweep.log */
-    q.band = c->plan[PLAN_BATCH].band != INT32_MIN ? c->plan[PLAN_BATCH].band
-        : (c->r2b_flat_k > 0 ? 0 : -1);
-    q.start_sleep = c->start_sleep > 0 ? c->start_sleep : 0;
-    q.flat_k = c->r2b_flat_k;
-    q.flat_px = c->r2b_flat_px;
-    q.flat_ld = c->r2b_flat_ld;
-    q.rows = c->r2b_rows;
-    q.nlist = 0;
-    for (int k = 0; k < 2; k++) {
-      q.sel_lo[k] = c->r2b_lo[k];
-      q.sel_hi[k] = c->r2b_hi[k];
+    /* the sibling direction (reference loop gst/bayer/gstrgb2bayer.c:254-268): up to kMaxList separately allocated
+     * frames per launch of the flat kernel; the tile kernel (MIBAYER_R2B_FLAT=0, tuning) has no table, nor has a
+     * frame beyond the flat kernel's 32-bit item index: those go frame by frame */
+    if (fs.is_list () && (c->r2b_flat_k <= 0 || (long long) f.height * (((f.width + 3) & ~3) / 4) > 0x7fffffffLL)) {
+      for (int k = 0; k < fs.n; k++) {
+        const int rc = launch_frames (c, FrameSet::strided (fs.srcs[k], c->src_bytes, fs.dsts[k], c->dst_bytes, 1),
+            stream);
+        if (rc != MIBAYER_OK)
+          return rc;
+      }
+      return MIBAYER_OK;
     }
-    const bool vec16 = (f.width % 4 == 0) && (f.src_stride % 16 == 0)
-        && aligned16 (d_src) && (nframes == 1 || src_frame_bytes % 16 == 0);
-    if (ntile_rows >= 0) {      /* band of 16-row units (host path) */
-      const long long y0 = tile_row0 * kInverseBandUnit;
-      long long y1 = (tile_row0 + ntile_rows) * kInverseBandUnit;
+    R2BParams q;
+    r2b_params (c, q);
+    fs.fill (q);
+    q.total_rows = fs.is_list () ? f.height : (long long) fs.n * f.height;
+    const bool vec16 = (f.width % 4 == 0) && (f.src_stride % 16 == 0) && fs.srcs16 ();
+    if (fs.is_list ()) {
+      HIP_TRY (launch_rgb2bayer_list (q, vec16, fs.dsts8 (), stream));
+    } else if (nrows >= 0) {    /* band of 16-row units (host path) */
+      const long long y0 = row0 * kInverseBandUnit;
+      long long y1 = (row0 + nrows) * kInverseBandUnit;
       if (y1 > q.total_rows)
         y1 = q.total_rows;
       HIP_TRY (launch_rgb2bayer (q, vec16, stream, y0, y1 - y0));
@@ -1113,20 +1206,17 @@ static int launch (const mibayer_ctx *c, const void *d_src,
     }
     return MIBAYER_OK;
   }
-  KParams p;
-  KernelFn kern;
-  unsigned grid;
-  Geometry g;
-  int rc = plan_launch (c, d_src, src_frame_bytes, d_dst, dst_frame_bytes,
-      nframes, p, kern, grid, &g, tile_row0, ntile_rows);
+  TileLaunch t;
+  const int rc = plan_launch (c, fs, t, row0, nrows);
   if (rc != MIBAYER_OK)
     return rc;
-  /* (lab builds) dynamic LDS per workgroup, only to cap the workgroups per CU in occupancy experiments */
+  /* (lab builds) dynamic LDS per workgroup, only to cap the workgroups per CU in occupancy experiments; not on
+   * list launches */
   static const unsigned dyn_lds = [] {
     const char *e = LAB_GETENV ("MIBAYER_DYN_LDS");
     return e ? (unsigned) atoi (e) : 0u;
   } ();
-  hipLaunchKernelGGL (kern, dim3 (grid), dim3 (g.var->threads), dyn_lds, stream, p);
+  hipLaunchKernelGGL (t.kern, dim3 (t.grid), dim3 (t.threads), fs.is_list () ? 0u : dyn_lds, stream, t.p);
   HIP_TRY (hipGetLastError ());
   return MIBAYER_OK;
 }
@@ -1836,18 +1926,15 @@ extern "C" int mibayer_launch_geometry (const mibayer_ctx *c, int nframes,
 {
   if (!c || nframes < 0 || c->deep)
     return MIBAYER_ERR_ARG;
-  KParams p;
-  KernelFn kern;
-  unsigned grid = 0;
-  Geometry g;
+  TileLaunch t;
   /* aligned dummy pointers: report the plan of the 16-byte fast path when the
    * geometry allows it */
-  int rc = plan_launch (c, (const void *) 256, c->src_bytes, (void *) 256,
-      c->dst_bytes, nframes > 0 ? nframes : 1, p, kern, grid, &g);
+  int rc = plan_launch (c, FrameSet::strided ((const void *) 256, c->src_bytes, (void *) 256, c->dst_bytes,
+          nframes > 0 ? nframes : 1), t);
   if (rc != MIBAYER_OK)
     return rc;
-  if (nframes == 0)
-    grid = 0;
+  const Geometry &g = t.g;
+  const unsigned grid = nframes == 0 ? 0 : t.grid;
   if (tile_w)
     *tile_w = g.var->tile_w;
   if (tile_h)
@@ -1876,7 +1963,7 @@ static int hist_params (const mibayer_ctx *c, const HistWin &w, HistParams *q)
   if (!c || c->inverse)
     return MIBAYER_ERR_ARG;
   const mibayer_cfg &f = c->cfg;
-  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const SampleFormat sf = sample_format (f);
   int x0 = w.x0, y0 = w.y0, ww = w.w, wh = w.h;
   if (x0 == 0 && y0 == 0 && ww == 0 && wh == 0) {
     ww = f.width;
@@ -1888,10 +1975,10 @@ static int hist_params (const mibayer_ctx *c, const HistWin &w, HistParams *q)
     return MIBAYER_ERR_GEOMETRY;
   memset (q, 0, sizeof *q);
   q->src_stride = f.src_stride;
-  q->in8 = bits == 0;
-  q->in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
-  q->mask2 = (bits ? (1u << bits) - 1u : 255u) * 0x00010001u;
-  q->shift = bits ? bits - 8 : 0;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
+  q->shift = sf.bits - 8;
   q->x0 = x0;
   q->x1 = x0 + ww;
   q->y0 = y0;
@@ -1913,28 +2000,42 @@ static int enqueue_hist (HistParams &q, const void *d_src, size_t src_frame_byte
 
 static void mark_dirty (mibayer_ctx *c, hipStream_t s);
 
-extern "C" int mibayer_hist_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes, int x0,
-    int y0, int w, int h, mibayer_hist *d_hist, void *hip_stream)
+/* mibayer_hist_device / mibayer_stats_device: a measurement over `nframes` device-resident mosaics into `d_out`, which
+ * has to be `out_align`-byte aligned.  `params (&q)` checks the entry point's own arguments and fills the kernel's,
+ * `enqueue (q)` zeroes the output and launches */
+template <typename Q, typename Params, typename Enqueue>
+static int measure_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes, const void *d_out,
+    unsigned out_align, const char *range, void *hip_stream, Params params, Enqueue enqueue)
 {
-  if (!c || !d_src || !d_hist || nframes < 0)
+  if (!c || !d_src || !d_out || nframes < 0)
     return MIBAYER_ERR_ARG;
-  const HistWin win = { 1, x0, y0, w, h };
-  HistParams q;
-  const int rc = hist_params (c, win, &q);
+  Q q;
+  const int rc = params (&q);
   if (rc != MIBAYER_OK)
     return rc;
   if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3)))
     return MIBAYER_ERR_GEOMETRY;
-  if ((((uintptr_t) d_src) | ((uintptr_t) d_hist)) & 3)
+  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_out) & (out_align - 1)))
     return MIBAYER_ERR_ARG;
   if (nframes == 0)
     return MIBAYER_OK;
   DeviceGuard guard (c->device);
   if (!guard.ok)
     return MIBAYER_ERR_HIP;
-  Range r ("mibayer:hist_device");
+  Range r (range);
   mark_dirty (c, (hipStream_t) hip_stream);
-  return enqueue_hist (q, d_src, src_frame_bytes, nframes, d_hist, (hipStream_t) hip_stream);
+  return enqueue (q);
+}
+
+extern "C" int mibayer_hist_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes, int x0,
+    int y0, int w, int h, mibayer_hist *d_hist, void *hip_stream)
+{
+  const HistWin win = { 1, x0, y0, w, h };
+  return measure_device<HistParams> (c, d_src, src_frame_bytes, nframes, d_hist, 4, "mibayer:hist_device", hip_stream,
+      [&] (HistParams *q) { return hist_params (c, win, q); },
+      [&] (HistParams &q) {
+        return enqueue_hist (q, d_src, src_frame_bytes, nframes, d_hist, (hipStream_t) hip_stream);
+      });
 }
 
 extern "C" int mibayer_set_hist (mibayer_ctx *c, int on, int x0, int y0, int w, int h)
@@ -2037,18 +2138,17 @@ static int stats_params (const mibayer_ctx *c, const StatsGrid &g, StatsParams *
   if (!c || c->inverse)
     return MIBAYER_ERR_ARG;
   const mibayer_cfg &f = c->cfg;
-  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
-  const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
+  const SampleFormat sf = sample_format (f);
   if (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1 || g.zones_y > MIBAYER_STATS_MAX_ZONES
-      || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.lo > g.hi || g.hi > vmax)
+      || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.lo > g.hi || g.hi > sf.vmax)
     return MIBAYER_ERR_ARG;
   memset (q, 0, sizeof *q);
   q->width = f.width;
   q->height = f.height;
   q->src_stride = f.src_stride;
-  q->in8 = bits == 0;
-  q->in_sel = (f.flags & MIBAYER_FLAG_SRC_BIG_ENDIAN) ? 0x02030001u : 0x03020100u;
-  q->mask2 = vmax * 0x00010001u;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
   q->lo = g.lo;
   q->hi = g.hi;
   q->zones_x = g.zones_x;
@@ -2074,29 +2174,16 @@ static int enqueue_stats (StatsParams &q, const void *d_src, size_t src_frame_by
 extern "C" int mibayer_stats_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes,
     int zones_x, int zones_y, uint32_t lo, uint32_t hi, mibayer_stats_zone *d_stats, void *hip_stream)
 {
-  if (!c || !d_src || !d_stats || nframes < 0)
-    return MIBAYER_ERR_ARG;
   StatsGrid g;
   g.zones_x = zones_x;
   g.zones_y = zones_y;
   g.lo = lo;
   g.hi = hi;
-  StatsParams q;
-  const int rc = stats_params (c, g, &q);
-  if (rc != MIBAYER_OK)
-    return rc;
-  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3)))
-    return MIBAYER_ERR_GEOMETRY;
-  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_stats) & 7))
-    return MIBAYER_ERR_ARG;
-  if (nframes == 0)
-    return MIBAYER_OK;
-  DeviceGuard guard (c->device);
-  if (!guard.ok)
-    return MIBAYER_ERR_HIP;
-  Range r ("mibayer:stats_device");
-  mark_dirty (c, (hipStream_t) hip_stream);
-  return enqueue_stats (q, d_src, src_frame_bytes, nframes, d_stats, (hipStream_t) hip_stream);
+  return measure_device<StatsParams> (c, d_src, src_frame_bytes, nframes, d_stats, 8, "mibayer:stats_device",
+      hip_stream, [&] (StatsParams *q) { return stats_params (c, g, q); },
+      [&] (StatsParams &q) {
+        return enqueue_stats (q, d_src, src_frame_bytes, nframes, d_stats, (hipStream_t) hip_stream);
+      });
 }
 
 extern "C" int mibayer_set_stats (mibayer_ctx *c, int zones_x, int zones_y, uint32_t lo, uint32_t hi)
@@ -2277,18 +2364,25 @@ static int ensure_ring (mibayer_ctx *c)
  * from frame to frame; they are patched into the instantiated graph
  * (hipGraphExecMemcpyNodeSetParams1D), or the graph is re-instantiated if the
  * runtime refuses the update. */
+/* an instantiated graph and the graph it was made from go together; a half-built pair has no exec yet */
+static void drop_graph (hipGraphExec_t &exec, hipGraph_t &graph)
+{
+  if (exec)
+    (void) hipGraphExecDestroy (exec);
+  if (graph)
+    (void) hipGraphDestroy (graph);
+  exec = nullptr;
+  graph = nullptr;
+}
+
 static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
     uint8_t *dst)
 {
   if (!s.s_graph)
     HIP_TRY (hipStreamCreateWithFlags (&s.s_graph, hipStreamNonBlocking));
-  if (s.exec && s.plan_epoch != c->plan_epoch) {
-    /* the plan has changed since the kernel node was built (the slot's previous frame has completed: it is free) */
-    (void) hipGraphExecDestroy (s.exec);
-    (void) hipGraphDestroy (s.graph);
-    s.exec = nullptr;
-    s.graph = nullptr;
-  }
+  /* the plan has changed since the kernel node was built (the slot's previous frame has completed: it is free) */
+  if (s.exec && s.plan_epoch != c->plan_epoch)
+    drop_graph (s.exec, s.graph);
   if (s.exec && (s.g_src != src || s.g_dst != dst)) {
     hipError_t e1 = hipGraphExecMemcpyNodeSetParams1D (s.exec, s.n_h2d,
         s.d_src, src, c->src_bytes, hipMemcpyHostToDevice);
@@ -2296,30 +2390,16 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
         s.d_dst, c->dst_bytes, hipMemcpyDeviceToHost);
     if (e1 != hipSuccess || e2 != hipSuccess) {
       (void) hipGetLastError ();
-      (void) hipGraphExecDestroy (s.exec);
-      (void) hipGraphDestroy (s.graph);
-      s.exec = nullptr;
-      s.graph = nullptr;
+      drop_graph (s.exec, s.graph);
     }
   }
   if (!s.exec) {
-    KParams p;
-    KernelFn kern;
-    unsigned grid;
-    Geometry g;
-    int rc = plan_launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1,
-        p, kern, grid, &g);
+    TileLaunch t;
+    int rc = plan_launch (c, slot_frame (c, s), t);
     if (rc != MIBAYER_OK)
       return rc;
-    void *args[1] = { &p };
-    hipKernelNodeParams kp;
-    memset (&kp, 0, sizeof kp);
-    kp.func = (void *) kern;
-    kp.gridDim = dim3 (grid);
-    kp.blockDim = dim3 ((unsigned) g.var->threads);
-    kp.sharedMemBytes = 0;
-    kp.kernelParams = args;
-    kp.extra = NULL;
+    void *args[1];
+    const hipKernelNodeParams kp = kernel_node_params (t, args);
     bool bad = hip_failed (hipGraphCreate (&s.graph, 0), "hipGraphCreate");
     bad = bad || hip_failed (hipGraphAddMemcpyNode1D (&s.n_h2d, s.graph, NULL,
             0, s.d_src, src, c->src_bytes, hipMemcpyHostToDevice),
@@ -2332,10 +2412,8 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
     bad = bad || hip_failed (hipGraphInstantiate (&s.exec, s.graph, NULL, NULL,
             0), "hipGraphInstantiate");
     if (bad) {                  /* no half-built graph survives a failure */
-      if (s.graph)
-        (void) hipGraphDestroy (s.graph);
-      s.graph = nullptr;
       s.exec = nullptr;
+      drop_graph (s.exec, s.graph);
       return MIBAYER_ERR_HIP;
     }
     s.plan_epoch = c->plan_epoch;
@@ -2351,6 +2429,31 @@ static int graph_submit (mibayer_ctx *c, Slot &s, const uint8_t *src,
 static int dst_planes (const mibayer_ctx *c)
 {
   return (c->cfg.flags & MIBAYER_FLAG_DST_PLANAR) ? 3 : 1;
+}
+
+/* the download of rows [y0, y1) of the frame in slot `s` to `dst` on the download queue; `row_bytes`: the bytes of a
+ * destination row that are written */
+static int download_frame (mibayer_ctx *c, const Slot &s, uint8_t *dst, size_t row_bytes, int y0, int y1)
+{
+  const mibayer_cfg &f = c->cfg;
+  const size_t stride = (size_t) f.dst_stride;
+  /* planar output: the rows of each of the three planes; the planes lie one under the other, so a whole frame is
+   * one run of height x planes rows */
+  const bool whole = y0 == 0 && y1 == f.height;
+  const int runs = whole ? 1 : dst_planes (c);
+  const size_t rows = whole ? (size_t) f.height * dst_planes (c) : (size_t) (y1 - y0);
+  for (int k = 0; k < runs; k++) {
+    const size_t doff = ((size_t) k * f.height + y0) * stride;
+    if (stride == row_bytes) {
+      HIP_TRY (hipMemcpyAsync (dst + doff, s.d_dst + doff, rows * stride, hipMemcpyDeviceToHost, c->s_d2h));
+    } else {
+      /* padded destination rows: only the written bytes of each row may be
+       * touched (the reference never writes the padding either) */
+      HIP_TRY (hipMemcpy2DAsync (dst + doff, stride, s.d_dst + doff, stride, row_bytes, rows,
+              hipMemcpyDeviceToHost, c->s_d2h));
+    }
+  }
+  return MIBAYER_OK;
 }
 
 /* Host path, one frame cut into horizontal bands: band b's kernel needs source
@@ -2421,8 +2524,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     }
     HIP_TRY (hipEventRecord (s.ev_band_in[b], c->s_h2d));
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_band_in[b], 0));
-    int rc = launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1,
-        c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
+    int rc = launch_frames (c, slot_frame (c, s), c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
     if (b == nb - 1) {          /* every row is on the device: the statistics once over the whole mosaic */
@@ -2432,20 +2534,9 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     }
     HIP_TRY (hipEventRecord (s.ev_band_kernel[b], c->s_compute));
     HIP_TRY (hipStreamWaitEvent (c->s_d2h, s.ev_band_kernel[b], 0));
-    /* planar output: the band is rows [y0, y1) of each of the three planes */
-    for (int k = 0; k < dst_planes (c); k++) {
-      const size_t doff = ((size_t) k * f.height + y0) * f.dst_stride;
-      if ((size_t) f.dst_stride == row_bytes) {
-        HIP_TRY (hipMemcpyAsync (dst + doff, s.d_dst + doff,
-                (size_t) (y1 - y0) * f.dst_stride, hipMemcpyDeviceToHost,
-                c->s_d2h));
-      } else {
-        /* padded destination rows: only the written bytes of each row */
-        HIP_TRY (hipMemcpy2DAsync (dst + doff, (size_t) f.dst_stride,
-                s.d_dst + doff, (size_t) f.dst_stride, row_bytes,
-                (size_t) (y1 - y0), hipMemcpyDeviceToHost, c->s_d2h));
-      }
-    }
+    rc = download_frame (c, s, dst, row_bytes, y0, y1);
+    if (rc != MIBAYER_OK)
+      return rc;
   }
   const int src_rc = slot_download_stats (c, s);
   if (src_rc != MIBAYER_OK)
@@ -2466,29 +2557,16 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
  * and the wait / record stay stream calls. */
 static int compute_graph_launch (mibayer_ctx *c, Slot &s)
 {
-  if (s.cexec && s.plan_epoch != c->plan_epoch) {       /* built under an older plan; the slot is free */
-    (void) hipGraphExecDestroy (s.cexec);
-    (void) hipGraphDestroy (s.cgraph);
-    s.cexec = nullptr;
-    s.cgraph = nullptr;
-  }
+  if (s.cexec && s.plan_epoch != c->plan_epoch)         /* built under an older plan; the slot is free */
+    drop_graph (s.cexec, s.cgraph);
   if (!s.cexec) {
     s.plan_epoch = c->plan_epoch;
-    KParams p;
-    KernelFn kern;
-    unsigned grid;
-    Geometry g;
-    const int rc = plan_launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes,
-        1, p, kern, grid, &g);
+    TileLaunch t;
+    const int rc = plan_launch (c, slot_frame (c, s), t);
     if (rc != MIBAYER_OK)
       return rc;
-    void *args[1] = { &p };
-    hipKernelNodeParams kp;
-    memset (&kp, 0, sizeof kp);
-    kp.func = (void *) kern;
-    kp.gridDim = dim3 (grid);
-    kp.blockDim = dim3 ((unsigned) g.var->threads);
-    kp.kernelParams = args;
+    void *args[1];
+    const hipKernelNodeParams kp = kernel_node_params (t, args);
     for (int with_events = 1; with_events >= 0 && !s.cexec; with_events--) {
       hipGraphNode_t n_wait = nullptr, n_kernel = nullptr, n_rec = nullptr;
       bool bad = hip_failed (hipGraphCreate (&s.cgraph, 0), "hipGraphCreate");
@@ -2505,10 +2583,8 @@ static int compute_graph_launch (mibayer_ctx *c, Slot &s)
               NULL, 0), "hipGraphInstantiate");
       if (bad) {
         (void) hipGetLastError ();
-        if (s.cgraph)
-          (void) hipGraphDestroy (s.cgraph);
-        s.cgraph = nullptr;
         s.cexec = nullptr;
+        drop_graph (s.cexec, s.cgraph);
         if (!with_events)
           return MIBAYER_ERR_HIP;
       } else {
@@ -2543,8 +2619,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
   } else {
     Range r ("mibayer:kernel");
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_in, 0));
-    const int rc = launch (c, s.d_src, c->src_bytes, s.d_dst, c->dst_bytes, 1,
-        c->s_compute, 0, -1, c->colour ? &s.stage : nullptr);
+    const int rc = launch_frames (c, slot_frame (c, s), c->s_compute, 0, -1, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
     const int stats_rc = slot_launch_stats (c, s);
@@ -2554,16 +2629,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
   }
   Range r ("mibayer:d2h");
   HIP_TRY (hipStreamWaitEvent (c->s_d2h, s.ev_kernel, 0));
-  if ((size_t) c->cfg.dst_stride == row_bytes) {
-    HIP_TRY (hipMemcpyAsync (dst, s.d_dst, c->dst_bytes, hipMemcpyDeviceToHost,
-            c->s_d2h));
-  } else {
-    /* padded destination rows: only the written bytes of each row may be
-     * touched (the reference never writes the padding either); planes lie one under the other */
-    HIP_TRY (hipMemcpy2DAsync (dst, (size_t) c->cfg.dst_stride, s.d_dst,
-            (size_t) c->cfg.dst_stride, row_bytes, (size_t) c->cfg.height * dst_planes (c),
-            hipMemcpyDeviceToHost, c->s_d2h));
-  }
+  const int rc = download_frame (c, s, dst, row_bytes, 0, c->cfg.height);
+  if (rc != MIBAYER_OK)
+    return rc;
   const int stats_rc = slot_download_stats (c, s);
   if (stats_rc != MIBAYER_OK)
     return stats_rc;
@@ -2595,28 +2663,15 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
   /* (the captured graphs hold the demosaic launch only: a frame with statistics is launched without them) */
   const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on;
-  if (want_graph && c->graph_mode == 1
-      && (size_t) c->cfg.dst_stride == row_bytes) {
-    rc = graph_submit (c, s, src, dst);
-    if (rc != MIBAYER_OK)
-      return rc;
-    s.tag = tag;
-    c->head = (c->head + 1) % (int) c->ring.size ();
-    c->pending++;
-    return MIBAYER_OK;
-  }
   /* bands pay when this frame has the link to itself (measured at 4K: +7 %
    * synchronous, -6 % with three frames in flight, which overlap anyway) */
-  if (c->host_bands > 1 && alone && c->pending == 0 && !want_graph) {
+  if (want_graph && c->graph_mode == 1
+      && (size_t) c->cfg.dst_stride == row_bytes)
+    rc = graph_submit (c, s, src, dst);
+  else if (c->host_bands > 1 && alone && c->pending == 0 && !want_graph)
     rc = enqueue_frame_banded (c, s, src, dst, row_bytes);
-    if (rc != MIBAYER_OK)
-      return rc;
-    s.tag = tag;
-    c->head = (c->head + 1) % (int) c->ring.size ();
-    c->pending++;
-    return MIBAYER_OK;
-  }
-  rc = enqueue_plain (c, s, src, dst, row_bytes, want_graph);
+  else
+    rc = enqueue_plain (c, s, src, dst, row_bytes, want_graph);
   if (rc != MIBAYER_OK)
     return rc;
   s.tag = tag;
@@ -2908,7 +2963,7 @@ extern "C" int mibayer_process_device (mibayer_ctx *c, const void *d_src,
     return MIBAYER_ERR_HIP;
   Range r ("mibayer:process_device");
   mark_dirty (c, (hipStream_t) hip_stream);
-  return launch (c, d_src, src_frame_bytes, d_dst, dst_frame_bytes, nframes,
+  return launch_frames (c, FrameSet::strided (d_src, src_frame_bytes, d_dst, dst_frame_bytes, nframes),
       (hipStream_t) hip_stream);
 }
 
@@ -2933,101 +2988,15 @@ extern "C" int mibayer_process_device_list (mibayer_ctx *c,
     return MIBAYER_ERR_HIP;
   Range r ("mibayer:process_device_list");
   mark_dirty (c, (hipStream_t) hip_stream);
-  if (c->deep) {
-    ColourStage stage;          /* one per call: every launch of a list of more than kMaxList frames takes the same */
-    if (c->colour)
-      colour_snapshot (c, &stage);
-    for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
-      DeepParams q = c->deep_args;
-      q.src = nullptr;
-      q.dst = nullptr;
-      q.nlist = nframes - f0 < kMaxList ? nframes - f0 : kMaxList;
-      for (int k = 0; k < q.nlist; k++) {
-        q.src_list[k] = (const uint8_t *) d_srcs[f0 + k];
-        q.dst_list[k] = (uint8_t *) d_dsts[f0 + k];
-      }
-      const int rc = launch_deep_kernel (c, q, q.nlist, (hipStream_t) hip_stream, 0, -1, c->colour ? &stage : nullptr);
-      if (rc != MIBAYER_OK)
-        return rc;
-    }
-    return MIBAYER_OK;
-  }
-  if (c->inverse) {
-    /* the sibling direction (reference loop gst/bayer/gstrgb2bayer.c:254-268): up to kMaxList separately allocated
-     * frames per launch of the flat kernel; the tile kernel (MIBAYER_R2B_FLAT=0, tuning) has no table and goes
-     * frame by frame */
-    const mibayer_cfg &f = c->cfg;
-    for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
-      const int n = nframes - f0 < kMaxList ? nframes - f0 : kMaxList;
-      if (c->r2b_flat_k <= 0 || (long long) f.height * (((f.width + 3) & ~3) / 4) > 0x7fffffffLL) {
-        for (int k = 0; k < n; k++) {
-          const int rc = launch (c, d_srcs[f0 + k], c->src_bytes, d_dsts[f0 + k],
-              c->dst_bytes, 1, (hipStream_t) hip_stream);
-          if (rc != MIBAYER_OK)
-            return rc;
-        }
-        continue;
-      }
-      R2BParams q;
-      q.src = nullptr;
-      q.dst = nullptr;
-      q.src_frame_bytes = 0;
-      q.dst_frame_bytes = 0;
-      q.width = f.width;
-      q.height = f.height;
-      q.src_stride = f.src_stride;
-      q.dst_stride = f.dst_stride;
-      q.out_dwords = ((f.width + 3) & ~3) / 4;
-      q.total_rows = f.height;
-      q.band = c->plan[PLAN_BATCH].band != INT32_MIN ? c->plan[PLAN_BATCH].band : 0;
-      q.start_sleep = c->start_sleep > 0 ? c->start_sleep : 0;
-      q.flat_k = c->r2b_flat_k;
-      q.flat_px = c->r2b_flat_px;
-      q.flat_ld = c->r2b_flat_ld;
-      q.rows = c->r2b_rows;
-      for (int k = 0; k < 2; k++) {
-        q.sel_lo[k] = c->r2b_lo[k];
-        q.sel_hi[k] = c->r2b_hi[k];
-      }
-      q.nlist = n;
-      bool src16 = true, dst8 = true;
-      for (int k = 0; k < n; k++) {
-        q.src_list[k] = (const uint8_t *) d_srcs[f0 + k];
-        q.dst_list[k] = (uint8_t *) d_dsts[f0 + k];
-        src16 = src16 && aligned16 (d_srcs[f0 + k]);
-        dst8 = dst8 && (((uintptr_t) d_dsts[f0 + k]) & 7u) == 0;
-      }
-      const bool vec16 = (f.width % 4 == 0) && (f.src_stride % 16 == 0) && src16;
-      HIP_TRY (launch_rgb2bayer_list (q, vec16, dst8, (hipStream_t) hip_stream));
-    }
-    return MIBAYER_OK;
-  }
+  ColourStage stage;            /* one per call: every launch of a list of more than kMaxList frames takes the same */
+  if (c->colour)
+    colour_snapshot (c, &stage);
   for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
     const int n = nframes - f0 < kMaxList ? nframes - f0 : kMaxList;
-    bool all16 = true, dst8 = true;
-    for (int f = 0; f < n; f++) {
-      all16 = all16 && aligned16 (d_srcs[f0 + f]) && aligned16 (d_dsts[f0 + f]);
-      dst8 = dst8 && (((uintptr_t) d_dsts[f0 + f]) & 7u) == 0;
-    }
-    KParams p;
-    KernelFn kern;
-    unsigned grid;
-    /* planned as a batch of n frames; the 16-byte path needs every pointer aligned */
-    Geometry g;
-    const int rc = plan_launch (c, d_srcs[f0], c->src_bytes, d_dsts[f0],
-        c->dst_bytes, n, p, kern, grid, &g, 0, -1, all16 ? 1 : (dst8 ? 2 : 0));
+    const int rc = launch_frames (c, FrameSet::list (d_srcs + f0, d_dsts + f0, n), (hipStream_t) hip_stream, 0, -1,
+        c->colour ? &stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
-    p.src = nullptr;
-    p.dst = nullptr;
-    p.nlist = n;
-    for (int f = 0; f < n; f++) {
-      p.src_list[f] = (const uint8_t *) d_srcs[f0 + f];
-      p.dst_list[f] = (uint8_t *) d_dsts[f0 + f];
-    }
-    hipLaunchKernelGGL (kern, dim3 (grid), dim3 (g.var->threads), 0,
-        (hipStream_t) hip_stream, p);
-    HIP_TRY (hipGetLastError ());
   }
   return MIBAYER_OK;
 }
@@ -3405,19 +3374,13 @@ extern "C" int mibayer_autotune (mibayer_ctx *c, const void *d_src,
   DeviceGuard guard (c->device);
   if (!guard.ok)
     return MIBAYER_ERR_HIP;
-  bool generic_off_grid = false;
-  {
-    KParams p;
-    KernelFn kern;
-    unsigned grid;
-    const int prc = plan_launch (c, d_src, src_frame_bytes, d_dst, dst_frame_bytes, nframes, p, kern, grid);
-    if (prc != MIBAYER_OK)
-      return prc;
-    generic_off_grid = kern != plan_for (c, nframes).var->fast && c->rows_off_sector;
-  }
+  TileLaunch t;
+  const int prc = plan_launch (c, FrameSet::strided (d_src, src_frame_bytes, d_dst, dst_frame_bytes, nframes), t);
+  if (prc != MIBAYER_OK)
+    return prc;
   return autotune_core (c, launch_class (c, nframes), [&] {
     return mibayer_process_device (c, d_src, src_frame_bytes, d_dst, dst_frame_bytes, nframes, c->s_compute);
-  }, generic_off_grid, report, report_len);
+  }, t.kern != t.g.var->fast && c->rows_off_sector, report, report_len);
 }
 
 /* The same over frames that are separate device allocations (mibayer_process_device_list): what a device-resident
@@ -3432,14 +3395,18 @@ extern "C" int mibayer_autotune_list (mibayer_ctx *c, const void *const *d_srcs,
   DeviceGuard guard (c->device);
   if (!guard.ok)
     return MIBAYER_ERR_HIP;
-  bool all16 = true;
-  for (int f = 0; f < nframes; f++) {
+  for (int f = 0; f < nframes; f++)
     if (!d_srcs[f] || !d_dsts[f])
       return MIBAYER_ERR_ARG;
-    all16 = all16 && aligned16 (d_srcs[f]) && aligned16 (d_dsts[f]);
+  bool fast = true;             /* every launch of the list takes the 16-byte kernel */
+  for (int f0 = 0; f0 < nframes; f0 += kMaxList) {
+    TileLaunch t;
+    const int prc = plan_launch (c, FrameSet::list (d_srcs + f0, d_dsts + f0,
+            nframes - f0 < kMaxList ? nframes - f0 : kMaxList), t);
+    if (prc != MIBAYER_OK)
+      return prc;
+    fast = fast && t.kern == t.g.var->fast;
   }
-  const mibayer_cfg &f = c->cfg;
-  const bool fast = all16 && (f.width % 16 == 0) && (f.src_stride % 16 == 0) && (f.dst_stride % 16 == 0);
   return autotune_core (c, launch_class (c, nframes < kMaxList ? nframes : kMaxList), [&] {
     return mibayer_process_device_list (c, d_srcs, d_dsts, nframes, c->s_compute);
   }, !fast && c->rows_off_sector, report, report_len);

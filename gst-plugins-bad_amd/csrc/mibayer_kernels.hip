@@ -1318,6 +1318,38 @@ static bool aligned_to (const void *ptr, unsigned a)
   return (((uintptr_t) ptr) & (a - 1)) == 0;
 }
 
+/* The flat-kernel launch of items [q.item0, q.item_end): of the batch as one sequence, or (q.nlist) of each frame of
+ * the list, every frame a whole number of blocks.  dst8: every destination 8-byte aligned (two items per store
+ * allowed).  false: this build has no flat kernel of that shape and nothing was launched */
+static bool launch_flat (R2BParams &q, bool vec16, bool dst8, hipStream_t stream, hipError_t *err)
+{
+  int px = q.flat_px == 8 ? 8 : 4;
+  /* two items per group: they must be in one row and the 8-byte store aligned */
+  if (px == 8 && ((q.out_dwords & 1) || (q.dst_stride & 7) || !dst8 || !vec16))
+    px = 4;
+  R2BFn fn = vec16 ? flat_kernel_for<16> (q.flat_k, px, q.flat_ld ? 1 : 0)
+      : flat_kernel_for<4> (q.flat_k, px, q.flat_ld ? 1 : 0);
+  if (!fn)
+    return false;
+  const long long items = (long long) q.item_end - q.item0;
+  const long long per_block = 256LL * q.flat_k * (px / 4);
+  long long nblocks = (items + per_block - 1) / per_block;
+  if (q.nlist) {
+    q.div_blocks_per_frame = make_fastdiv ((uint32_t) nblocks);
+    nblocks *= q.nlist;
+  }
+  if (q.band < 0)               /* one contiguous chunk of the launch per XCD */
+    q.band = (int) ((nblocks + kNumXcd - 1) / kNumXcd);
+  const long long grid = grid_blocks_for (1, nblocks, q.band);
+  *err = hipErrorInvalidValue;
+  if (grid <= 0x7fffffffLL) {
+    q.map = make_tile_map (1, 1, nblocks, q.band, 0);
+    hipLaunchKernelGGL (fn, dim3 ((unsigned) grid), dim3 (256), 0, stream, q);
+    *err = hipGetLastError ();
+  }
+  return true;
+}
+
 hipError_t launch_rgb2bayer (const R2BParams &p, bool vec16, hipStream_t stream,
     long long row0, long long nrows)
 {
@@ -1338,28 +1370,11 @@ hipError_t launch_rgb2bayer (const R2BParams &p, bool vec16, hipStream_t stream,
   /* ---- flat kernel ---------------------------------------------------------- */
   const long long item_end = (row0 + nrows) * p.out_dwords;
   if (q.flat_k > 0 && item_end <= 0x7fffffffLL) {
-    int px = q.flat_px == 8 ? 8 : 4;
-    /* two items per group: they must be in one row and the 8-byte store aligned */
-    if (px == 8 && ((p.out_dwords & 1) || (p.dst_stride & 7) || (p.dst_frame_bytes & 7)
-            || !aligned_to (p.dst, 8) || !vec16))
-      px = 4;
-    R2BFn fn = vec16 ? flat_kernel_for<16> (q.flat_k, px, q.flat_ld ? 1 : 0)
-        : flat_kernel_for<4> (q.flat_k, px, q.flat_ld ? 1 : 0);
-    if (fn) {
-      q.item0 = (uint32_t) (row0 * p.out_dwords);
-      q.item_end = (uint32_t) item_end;
-      const long long items = item_end - q.item0;
-      const long long per_block = 256LL * q.flat_k * (px / 4);
-      const long long nblocks = (items + per_block - 1) / per_block;
-      if (q.band < 0)           /* one contiguous chunk of the launch per XCD */
-        q.band = (int) ((nblocks + kNumXcd - 1) / kNumXcd);
-      const long long grid = grid_blocks_for (1, nblocks, q.band);
-      if (grid > 0x7fffffffLL)
-        return hipErrorInvalidValue;
-      q.map = make_tile_map (1, 1, nblocks, q.band, 0);
-      hipLaunchKernelGGL (fn, dim3 ((unsigned) grid), dim3 (256), 0, stream, q);
-      return hipGetLastError ();
-    }
+    q.item0 = (uint32_t) (row0 * p.out_dwords);
+    q.item_end = (uint32_t) item_end;
+    hipError_t err;
+    if (launch_flat (q, vec16, !(p.dst_frame_bytes & 7) && aligned_to (p.dst, 8), stream, &err))
+      return err;
   }
 
   /* ---- tile kernel ------------------------------------------------------------ */
@@ -1413,27 +1428,10 @@ hipError_t launch_rgb2bayer_list (const R2BParams &p, bool vec16, bool dst8, hip
   const long long items = (long long) p.height * p.out_dwords;
   if (items > 0x7fffffffLL)
     return hipErrorInvalidValue;
-  int px = q.flat_px == 8 ? 8 : 4;
-  if (px == 8 && ((p.out_dwords & 1) || (p.dst_stride & 7) || !dst8 || !vec16))
-    px = 4;
-  R2BFn fn = vec16 ? flat_kernel_for<16> (q.flat_k, px, q.flat_ld ? 1 : 0)
-      : flat_kernel_for<4> (q.flat_k, px, q.flat_ld ? 1 : 0);
-  if (!fn)
-    return hipErrorInvalidValue;
   q.item0 = 0;
   q.item_end = (uint32_t) items;
-  const long long per_block = 256LL * q.flat_k * (px / 4);
-  const long long bpf = (items + per_block - 1) / per_block;
-  q.div_blocks_per_frame = make_fastdiv ((uint32_t) bpf);
-  const long long nblocks = bpf * p.nlist;
-  if (q.band < 0)
-    q.band = (int) ((nblocks + kNumXcd - 1) / kNumXcd);
-  const long long grid = grid_blocks_for (1, nblocks, q.band);
-  if (grid > 0x7fffffffLL)
-    return hipErrorInvalidValue;
-  q.map = make_tile_map (1, 1, nblocks, q.band, 0);
-  hipLaunchKernelGGL (fn, dim3 ((unsigned) grid), dim3 (256), 0, stream, q);
-  return hipGetLastError ();
+  hipError_t err;
+  return launch_flat (q, vec16, dst8, stream, &err) ? err : hipErrorInvalidValue;
 }
 
 /* ------------------------------------------------------------------------- */

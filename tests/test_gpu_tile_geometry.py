@@ -204,6 +204,50 @@ def test_aligned_arm_every_shift(gpu_pkg, oracle, name):
     assert not bad, "\n".join(bad)
 
 
+@pytest.mark.parametrize("align", [64, 128])
+def test_aligned_arm_over_a_list_of_8_byte_aligned_destinations(gpu_pkg, gpu_lab_pkg, oracle, align):
+    """five separately allocated frames of 642x50 whose destinations are all 8-byte aligned but not all 16-byte
+    aligned: neither the fast arm nor a grid to sit on, so the list launch takes the sector-aligned arm (64: the lab
+    build's flavour).  Every destination has its own guard bytes on both sides"""
+    pkg = gpu_lab_pkg if align == 64 else gpu_pkg
+    name, (w, h), n = "lds_2x4_r4_dpp_nt", (642, 50), 5
+    offs = (0, 8, 16, 24, 72)
+    case = tc.rotate(align // 64, w, h)
+    sstride = tc.src_stride_of(w)
+    src = random_frames(7, w, h, n, sstride)
+    want = wanted(oracle, pkg, ("random", 7, sstride, n), src, case)
+    with pkg.Context(w, h, case.order, case.layout, src_stride=sstride, device=0) as ctx:
+        assert ctx.dst_stride == 4 * w and ctx.dst_stride % 8 == 0
+        ctx.set_plan(tc.variant_id(pkg, name), 1, align)
+        assert ctx.get_plan() == (tc.variant_id(pkg, name), 1, align)
+        total = ctx.dst_bytes + 2 * GUARD + SLACK
+        srcs = [ctx.device_alloc(ctx.src_bytes) for _ in range(n)]
+        dsts = [ctx.device_alloc(total) for _ in range(n)]
+        try:
+            assert all(d % 128 == 0 for d in dsts), "the offsets assume allocations at 0 mod 128"
+            for d, s in zip(srcs, src):
+                ctx.to_device(d, s)
+            for d in dsts:
+                ctx.to_device(d, np.full(total, FILL, np.uint8))
+            ptrs = [d + GUARD + o for d, o in zip(dsts, offs)]
+            assert all(p % 8 == 0 for p in ptrs) and any(p % 16 for p in ptrs)
+            ctx.process_device_list(srcs, ptrs)
+            ctx.sync()
+            raw = [ctx.from_device(d, total) for d in dsts]
+        finally:
+            for d in srcs + dsts:
+                ctx.device_free(d)
+    bad = []
+    for f, (r, o) in enumerate(zip(raw, offs)):
+        lo = GUARD + o
+        if not ((r[:lo] == FILL).all() and (r[lo + ctx.dst_bytes:] == FILL).all()):
+            bad.append("frame %d: guard bytes written" % f)
+        got = r[lo:lo + ctx.dst_bytes].reshape(h, 4 * w)
+        if not np.array_equal(got, want[f]):
+            bad.append("frame %d (destination at %d mod 128): %s" % (f, o, first_difference(got, want[f])))
+    assert not bad, "\n".join(bad)
+
+
 # -- 5. block orders -------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fast", [False, True], ids=["generic", "fast"])
