@@ -767,6 +767,17 @@ class Context:
         fn.restype, fn.argtypes = ctypes.c_int, [_vp, ctypes.c_int]
         _check(fn(self._h, ms), "mibayer_internal_stall")
 
+    @property
+    def host_bands(self):
+        """Seam (csrc/mibayer_hooks.h): the bands the next host-path frame submitted alone would be cut into."""
+        if not hasattr(lib(), "mibayer_internal_host_bands"):
+            raise MibayerErrorNoLib("the band count is exported by the lab build only (make lab; MIBAYER_LIB_PATH)")
+        fn = lib().mibayer_internal_host_bands
+        fn.restype, fn.argtypes = ctypes.c_int, [_vp]
+        nb = fn(self._h)
+        _check(min(nb, OK), "mibayer_internal_host_bands")
+        return nb
+
     # -- device path ------------------------------------------------------------------------
     def device_alloc(self, nbytes):
         p = lib().mibayer_device_alloc(self._h, nbytes)

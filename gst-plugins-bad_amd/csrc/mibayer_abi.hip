@@ -2906,6 +2906,11 @@ extern "C" int mibayer_internal_stall (mibayer_ctx *c, int ms)
   return MIBAYER_OK;
 }
 
+extern "C" int mibayer_internal_host_bands (const mibayer_ctx *c)
+{
+  return c ? c->host_bands : MIBAYER_ERR_ARG;
+}
+
 extern "C" int mibayer_set_wait_spin (mibayer_ctx *c, int spin_us)
 {
   if (!c)

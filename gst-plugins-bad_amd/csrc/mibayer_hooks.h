@@ -86,6 +86,11 @@ int mibayer_internal_settled (mibayer_ctx *ctx);
  * shared) completes only afterwards.  Tests and mibayer_pool_inject_stall(). */
 int mibayer_internal_stall (mibayer_ctx *ctx, int ms);
 
+/* The horizontal bands the next host-path frame would be cut into if it were submitted alone (1: not banded); the
+ * count follows the geometry, the plan and -- lab build -- MIBAYER_HOST_BANDS.  NULL: MIBAYER_ERR_ARG.  Tests
+ * (tests/band_cases.py holds the rule). */
+int mibayer_internal_host_bands (const mibayer_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ def test_the_dynamic_symbol_table_is_exactly_the_header(pkg):
     assert exported(pkg.LIB_PATH) == syms
     hooks = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "gst-plugins-bad_amd", "csrc", "mibayer_hooks.h")).read(), flags=re.S)
     seam = sorted(set(re.findall(r"\b(mibayer_internal_[a-z0-9_]+)\s*\(", hooks)))
-    assert len(seam) == 6
+    assert len(seam) == 7
     if os.path.exists(pkg.LAB_LIB_PATH):
         assert exported(pkg.LAB_LIB_PATH) == sorted(syms + seam)
     # the header says which entry points are the drop-in and which are tuning / diagnostics: every function is in
