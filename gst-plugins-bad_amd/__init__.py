@@ -180,6 +180,48 @@ def stats_grey_world(zones, pattern, black=None):
     return rc, tuple(gains)
 
 
+SHADING_MAX_NODES = 129
+
+
+class Shading(ctypes.Structure):
+    """struct mibayer_shading (include/mibayer.h): cells of (1 << kx) x (1 << ky) pixels, a black level per CFA site
+    and the Q12 gain table g[site][ny][nx] (host memory; the library copies it).  Shading(kx, ky, table, black) keeps
+    the array alive as long as the structure lives."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("cell_log2_x", ctypes.c_int32), ("cell_log2_y", ctypes.c_int32),
+                ("black", ctypes.c_uint32 * 4), ("table", ctypes.c_void_p)]
+
+    def __init__(self, kx=4, ky=4, table=None, black=(0, 0, 0, 0)):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(Shading)
+        self.cell_log2_x, self.cell_log2_y = int(kx), int(ky)
+        self.black[:] = [int(v) for v in black]
+        self._table = None if table is None else np.ascontiguousarray(table, np.uint16)
+        self.table = None if table is None else self._table.ctypes.data
+
+
+def shading_nodes(width, height, kx, ky):
+    """mibayer_shading_nodes: (nx, ny) of a width x height frame (no device needed)"""
+    nx, ny = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().mibayer_shading_nodes(int(width), int(height), int(kx), int(ky), ctypes.byref(nx), ctypes.byref(ny)),
+           "mibayer_shading_nodes")
+    return nx.value, ny.value
+
+
+def stats_shading(zones, width, height, black, kx, ky, max_gain):
+    """mibayer_stats_shading: (ok, (4, ny, nx) uint16 Q12 table) from the (zones_y, zones_x) STATS_DTYPE zones of a flat
+    field; black may be None (no device needed)"""
+    zones = np.ascontiguousarray(zones, STATS_DTYPE)
+    zones_y, zones_x = zones.shape
+    nx, ny = shading_nodes(width, height, kx, ky)
+    out = np.zeros((4, ny, nx), np.uint16)
+    b = None if black is None else (ctypes.c_uint32 * 4)(*[int(v) for v in black])
+    rc = lib().mibayer_stats_shading(_ptr(zones), zones_x, zones_y, int(width), int(height), b, int(kx), int(ky),
+                                     float(max_gain), _ptr(out))
+    if rc < 0:
+        raise MibayerError(rc, "mibayer_stats_shading")
+    return rc, out
+
+
 HIST_BINS = 256
 
 
@@ -358,6 +400,15 @@ ABI = {
     "mibayer_hist_exposure": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
                                              ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
+    "mibayer_shading_nodes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "mibayer_set_shading": (ctypes.c_int, [_vp, ctypes.POINTER(Shading)]),
+    "mibayer_get_shading": (ctypes.c_int, [_vp, ctypes.POINTER(Shading)]),
+    "mibayer_shade_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "mibayer_pool_set_shading": (ctypes.c_int, [_vp, ctypes.POINTER(Shading)]),
+    "mibayer_stats_shading": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_double, _vp]),
 }
 
 
@@ -508,6 +559,12 @@ class Pool:
         _check(lib().mibayer_pool_frame_hist(self._h, _ptr(out)), "mibayer_pool_frame_hist")
         return out
 
+    def set_shading(self, shading):
+        """mibayer_pool_set_shading: the lens shading table (a Shading, or None = off) of the frames submitted from
+        now on"""
+        _check(lib().mibayer_pool_set_shading(self._h, None if shading is None else ctypes.byref(shading)),
+               "mibayer_pool_set_shading")
+
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_pool_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_pool_submit")
 
@@ -618,6 +675,31 @@ class Context:
         out = Colour()
         _check(lib().mibayer_get_colour(self._h, ctypes.byref(out)), "mibayer_get_colour")
         return out
+
+    # -- lens shading correction ------------------------------------------------------------
+    def set_shading(self, shading):
+        """mibayer_set_shading: the table (a Shading, or None = off) of the host-path frames accepted and the
+        shade_device calls made from now on"""
+        _check(lib().mibayer_set_shading(self._h, None if shading is None else ctypes.byref(shading)),
+               "mibayer_set_shading")
+
+    def get_shading(self):
+        """mibayer_get_shading: None when no table is set, else (kx, ky, black, (4, ny, nx) table)"""
+        out = Shading()
+        rc = lib().mibayer_get_shading(self._h, ctypes.byref(out))
+        if rc == ERR_EMPTY:
+            return None
+        _check(rc, "mibayer_get_shading")
+        nx, ny = shading_nodes(self.width, self.height, out.cell_log2_x, out.cell_log2_y)
+        table = np.ctypeslib.as_array(ctypes.cast(out.table, ctypes.POINTER(ctypes.c_uint16)), (4, ny, nx)).copy()
+        return out.cell_log2_x, out.cell_log2_y, tuple(out.black), table
+
+    def shade_device(self, d_src, d_dst=None, nframes=1, src_frame_bytes=None, dst_frame_bytes=None, stream="ctx"):
+        """mibayer_shade_device: nframes mosaics at d_src shaded into d_dst (None: in place) with the table set"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        pitch = src_frame_bytes or self.src_bytes
+        _check(lib().mibayer_shade_device(self._h, _vp(d_src), pitch, _vp(d_src if d_dst is None else d_dst),
+                                          (dst_frame_bytes or pitch), nframes, _vp(s)), "mibayer_shade_device")
 
     # -- mosaic zone statistics -------------------------------------------------------------
     def stats_device(self, d_src, d_stats, zones_x, zones_y, lo, hi, nframes=1, src_frame_bytes=None, stream="ctx"):

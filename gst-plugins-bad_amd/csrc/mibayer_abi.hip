@@ -20,6 +20,7 @@
 #include <atomic>
 #include <limits.h>
 #include <math.h>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdio.h>
@@ -146,6 +147,16 @@ struct HistWin {
 constexpr int kMaxHostBands = 8;
 constexpr int kInverseBandUnit = 16;    /* rows; a multiple of every rows-per-block of the rgb2bayer kernel */
 
+/* a shading table as set (mibayer_set_shading): the parameters, the host copy and the device copy the kernel reads */
+struct ShadeTable {
+  mibayer_shading par;          /* par.table = host.data () */
+  int nx = 0, ny = 0;
+  int device = 0;
+  std::vector<uint16_t> host;
+  uint16_t *d_table = nullptr;
+  ~ShadeTable ();
+};
+
 struct Slot {
   uint8_t *d_src = nullptr;
   uint8_t *d_dst = nullptr;
@@ -180,6 +191,9 @@ struct Slot {
   mibayer_stats_zone *d_stats = nullptr;
   mibayer_stats_zone *h_stats = nullptr;
   HistWin win;                    /* mibayer_set_hist: likewise */
+  /* mibayer_set_shading: the table of the frame in the slot (NULL: none), taken when the frame is accepted like the
+   * stage; the reference keeps its device copy alive while the frame's launches may read it */
+  std::shared_ptr<const ShadeTable> shade;
 };
 
 int device_count_cached ()
@@ -332,6 +346,7 @@ struct mibayer_ctx {
   HistWin hist_win;                     /* mibayer_set_hist / mibayer_frame_hist: likewise, under stats_mu */
   bool last_hist_on = false;
   mibayer_hist last_hist;
+  std::shared_ptr<const ShadeTable> shading;    /* mibayer_set_shading (NULL: off), under stats_mu */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -2222,11 +2237,15 @@ extern "C" int mibayer_frame_stats (mibayer_ctx *c, mibayer_stats_zone *out, int
 /* a frame is accepted into slot `s`: its grid, and the slot's zone buffers when it has one */
 static int slot_take_stats (mibayer_ctx *c, Slot &s)
 {
+  std::shared_ptr<const ShadeTable> shade;
   {
     std::lock_guard<std::mutex> lk (c->stats_mu);
     s.grid = c->stats_grid;
     s.win = c->hist_win;
+    shade = c->shading;
   }
+  s.shade.swap (shade);         /* the slot's old table may go here (hipFree waits for the device): outside the lock */
+  shade.reset ();
   if (s.grid.zones_x == 0 && !s.win.on)
     return MIBAYER_OK;
   if (!s.d_stats)
@@ -2309,6 +2328,255 @@ extern "C" int mibayer_stats_grey_world (const mibayer_stats_zone *zones, int nz
   const double r = m[1] / m[0], b = m[1] / m[2];
   gains[0] = r < 1.0 / 16 ? 1.0 / 16 : r > 15.99 ? 15.99 : r;
   gains[2] = b < 1.0 / 16 ? 1.0 / 16 : b > 15.99 ? 15.99 : b;
+  return 1;
+}
+
+/* ---- lens shading correction (group `shading`) ------------------------------------------ */
+
+/* hipFree waits for the device: the launches that read the table have completed when it returns.  While a device has
+ * stopped answering nothing may block behind it, and the table (at most 130 KiB) is left to the runtime */
+ShadeTable::~ShadeTable ()
+{
+  if (!d_table || g_wedges_open.load () != 0)
+    return;
+  DeviceGuard guard (device);
+  if (guard.ok)
+    (void) hipFree (d_table);
+}
+
+extern "C" int mibayer_shading_nodes (int width, int height, int kx, int ky, int *nx, int *ny)
+{
+  if (!nx || !ny || width < 1 || height < 1 || kx < 2 || kx > 8 || ky < 2 || ky > 8)
+    return MIBAYER_ERR_ARG;
+  const int x = ((width - 1) >> kx) + 2, y = ((height - 1) >> ky) + 2;
+  if (x > MIBAYER_SHADING_MAX_NODES || y > MIBAYER_SHADING_MAX_NODES)
+    return MIBAYER_ERR_ARG;
+  *nx = x;
+  *ny = y;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_set_shading (mibayer_ctx *c, const mibayer_shading *sh)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const ShadeTable> next;
+  if (sh) {
+    int nx, ny;
+    if (sh->struct_size != sizeof (mibayer_shading) || !sh->table
+        || mibayer_shading_nodes (c->cfg.width, c->cfg.height, sh->cell_log2_x, sh->cell_log2_y, &nx, &ny) != MIBAYER_OK)
+      return MIBAYER_ERR_ARG;
+    const uint32_t vmax = sample_format (c->cfg).vmax;
+    for (int s = 0; s < 4; s++)
+      if (sh->black[s] > vmax)
+        return MIBAYER_ERR_ARG;
+    const size_t n = (size_t) 4 * (size_t) ny * (size_t) nx;
+    for (size_t e = 0; e < n; e++)
+      if (sh->table[e] > 32767)
+        return MIBAYER_ERR_ARG;
+    std::shared_ptr<ShadeTable> t (new (std::nothrow) ShadeTable);
+    if (!t)
+      return MIBAYER_ERR_NOMEM;
+    t->host.assign (sh->table, sh->table + n);
+    t->par = *sh;
+    t->par.table = t->host.data ();
+    t->nx = nx;
+    t->ny = ny;
+    t->device = c->device;
+    DeviceGuard guard (c->device);
+    if (!guard.ok)
+      return MIBAYER_ERR_HIP;
+    HIP_TRY (hipMalloc ((void **) &t->d_table, n * sizeof (uint16_t)));
+    HIP_TRY (hipMemcpy (t->d_table, t->host.data (), n * sizeof (uint16_t), hipMemcpyHostToDevice));
+    next = t;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->shading.swap (next);       /* the table replaced goes when the last frame that took it has gone */
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_get_shading (const mibayer_ctx *c, mibayer_shading *out)
+{
+  if (!c || !out || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (!c->shading) {
+    memset (out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    return MIBAYER_ERR_EMPTY;
+  }
+  *out = c->shading->par;
+  return MIBAYER_OK;
+}
+
+/* the kernel's arguments for table `t` on context `c`, rows [y0, y1) */
+static void shade_params (const mibayer_ctx *c, const ShadeTable &t, int y0, int y1, ShadeParams *q)
+{
+  const mibayer_cfg &f = c->cfg;
+  const SampleFormat sf = sample_format (f);
+  memset (q, 0, sizeof *q);
+  q->table = t.d_table;
+  q->width = f.width;
+  q->height = f.height;
+  q->src_stride = q->dst_stride = f.src_stride;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
+  q->vmax = (int) sf.vmax;
+  q->kx = t.par.cell_log2_x;
+  q->ky = t.par.cell_log2_y;
+  q->nx = t.nx;
+  q->ny = t.ny;
+  for (int s = 0; s < 4; s++)
+    q->black[s] = (int) t.par.black[s];
+  q->y0 = y0;
+  q->y1 = y1;
+}
+
+extern "C" int mibayer_shade_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream)
+{
+  if (!c || c->inverse || !d_src || !d_dst || nframes < 0)
+    return MIBAYER_ERR_ARG;
+  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3) || dst_frame_bytes < c->src_bytes
+          || (dst_frame_bytes & 3)))
+    return MIBAYER_ERR_GEOMETRY;
+  /* in place means frame for frame: with two pitches a frame's stores would land in samples another frame has yet to read */
+  if (nframes > 1 && d_dst == d_src && dst_frame_bytes != src_frame_bytes)
+    return MIBAYER_ERR_GEOMETRY;
+  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_dst) & 3))
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const ShadeTable> t;
+  {
+    std::lock_guard<std::mutex> lk (c->stats_mu);
+    t = c->shading;
+  }
+  if (!t)
+    return MIBAYER_ERR_EMPTY;
+  if (nframes == 0)
+    return MIBAYER_OK;
+  DeviceGuard guard (c->device);
+  if (!guard.ok)
+    return MIBAYER_ERR_HIP;
+  Range r ("mibayer:shade_device");
+  mark_dirty (c, (hipStream_t) hip_stream);
+  ShadeParams q;
+  shade_params (c, *t, 0, c->cfg.height, &q);
+  q.src = (const uint8_t *) d_src;
+  q.dst = (uint8_t *) d_dst;
+  q.src_frame_bytes = src_frame_bytes;
+  q.dst_frame_bytes = dst_frame_bytes;
+  HIP_TRY (launch_shade (q, nframes, (hipStream_t) hip_stream));
+  return MIBAYER_OK;
+}
+
+/* rows [y0, y1) of the frame in slot `s`, in place on its device mosaic, on the compute queue: behind the upload of
+ * those rows and before anything reads them */
+static int slot_launch_shade (mibayer_ctx *c, Slot &s, int y0, int y1)
+{
+  if (!s.shade || y1 <= y0)
+    return MIBAYER_OK;
+  Range r ("mibayer:shade");
+  ShadeParams q;
+  shade_params (c, *s.shade, y0, y1, &q);
+  q.src = q.dst = s.d_src;
+  q.src_frame_bytes = q.dst_frame_bytes = c->src_bytes;
+  HIP_TRY (launch_shade (q, 1, c->s_compute));
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_stats_shading (const mibayer_stats_zone *zones, int zones_x, int zones_y, int width, int height,
+    const uint32_t black[4], int kx, int ky, double max_gain, uint16_t *table_out)
+{
+#pragma clang fp contract(off)
+  int nx, ny;
+  if (!zones || !table_out || width < 2 || (width & 1) || height < 1 || zones_x < 1 || zones_x > MIBAYER_STATS_MAX_ZONES
+      || zones_y < 1 || zones_y > MIBAYER_STATS_MAX_ZONES || zones_x > width / 2 || zones_y > height / 2
+      || mibayer_shading_nodes (width, height, kx, ky, &nx, &ny) != MIBAYER_OK || !(max_gain >= 1.0 && max_gain <= 7.99))
+    return MIBAYER_ERR_ARG;
+  const size_t plane = (size_t) ny * (size_t) nx;
+  for (size_t e = 0; e < 4 * plane; e++)
+    table_out[e] = 4096;
+  const int zcw = 2 * ((width / 2 + zones_x - 1) / zones_x), zch = 2 * (((height + 1) / 2 + zones_y - 1) / zones_y);
+  const int ux = (width + zcw - 1) / zcw, uy = (height + zch - 1) / zch;
+  std::vector<double> cx ((size_t) ux), cy ((size_t) uy), m ((size_t) ux * uy), v (plane);
+  std::vector<uint16_t> res (4 * plane);
+  std::vector<char> full ((size_t) ux * uy);
+  for (int a = 0; a < ux; a++)
+    cx[(size_t) a] = (double) (a * zcw + ((a + 1) * zcw < width ? (a + 1) * zcw : width)) * 0.5;
+  for (int b = 0; b < uy; b++)
+    cy[(size_t) b] = (double) (b * zch + ((b + 1) * zch < height ? (b + 1) * zch : height)) * 0.5;
+  /* index and weight along one axis */
+  auto locate = [] (const std::vector<double> &c, double p, int *lo, int *hi, double *t) {
+    const int n = (int) c.size ();
+    *t = 0.0;
+    if (n == 1 || p <= c[0]) {
+      *lo = 0;
+    } else if (p >= c[(size_t) n - 1]) {
+      *lo = n - 1;
+    } else {
+      int a = 0;
+      while (c[(size_t) a + 1] <= p)
+        a++;
+      *lo = a;
+      *t = (p - c[(size_t) a]) / (c[(size_t) a + 1] - c[(size_t) a]);
+    }
+    *hi = *lo + 1 < n ? *lo + 1 : n - 1;
+  };
+  for (int s = 0; s < 4; s++) {
+    bool any = false;
+    for (int b = 0; b < uy; b++)
+      for (int a = 0; a < ux; a++) {
+        const mibayer_stats_zone &z = zones[(size_t) b * zones_x + a];
+        const size_t e = (size_t) b * ux + a;
+        full[e] = z.count[s] > 0;
+        any = any || full[e];
+        m[e] = full[e] ? (double) z.sum[s] / (double) z.count[s] - (black ? (double) black[s] : 0.0) : 0.0;
+      }
+    if (!any)
+      return 0;
+    for (int b = 0; b < uy; b++)
+      for (int a = 0; a < ux; a++) {
+        if (full[(size_t) b * ux + a])
+          continue;
+        long long best = -1;
+        size_t from = 0;
+        for (int b2 = 0; b2 < uy; b2++)
+          for (int a2 = 0; a2 < ux; a2++) {
+            const long long d = (long long) (a2 - a) * (a2 - a) + (long long) (b2 - b) * (b2 - b);
+            if (full[(size_t) b2 * ux + a2] && (best < 0 || d < best)) {
+              best = d;
+              from = (size_t) b2 * ux + a2;
+            }
+          }
+        m[(size_t) b * ux + a] = m[from];
+      }
+    double vmax = 0.0;
+    for (int j = 0; j < ny; j++) {
+      int b, b1;
+      double ty;
+      locate (cy, (double) (j << ky), &b, &b1, &ty);
+      for (int i = 0; i < nx; i++) {
+        int a, a1;
+        double tx;
+        locate (cx, (double) (i << kx), &a, &a1, &tx);
+        const double m00 = m[(size_t) b * ux + a], m01 = m[(size_t) b * ux + a1];
+        const double m10 = m[(size_t) b1 * ux + a], m11 = m[(size_t) b1 * ux + a1];
+        const double top = m00 + (m01 - m00) * tx, bot = m10 + (m11 - m10) * tx;
+        const double val = top + (bot - top) * ty;
+        if (!(val > 0.0))
+          return 0;
+        v[(size_t) j * nx + i] = val;
+        vmax = val > vmax ? val : vmax;
+      }
+    }
+    for (size_t e = 0; e < plane; e++) {
+      double gain = vmax / v[e];
+      gain = gain < 1.0 ? 1.0 : gain > max_gain ? max_gain : gain;
+      res[(size_t) s * plane + e] = (uint16_t) floor (gain * 4096.0 + 0.5);
+    }
+  }
+  memcpy (table_out, res.data (), res.size () * sizeof (uint16_t));
   return 1;
 }
 
@@ -2515,6 +2783,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     const int y0 = t0 * th;
     const int y1 = t1 * th < f.height ? t1 * th : f.height;
     const int up_to = y1 + halo < f.height ? y1 + halo : f.height;     /* + the halo row below */
+    const int shade_from = uploaded;    /* the rows this band's upload brings: shaded once, before anything reads them */
     if (up_to > uploaded) {
       const size_t off = (size_t) uploaded * f.src_stride;
       HIP_TRY (hipMemcpyAsync (s.d_src + off, src + off,
@@ -2524,7 +2793,10 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     }
     HIP_TRY (hipEventRecord (s.ev_band_in[b], c->s_h2d));
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_band_in[b], 0));
-    int rc = launch_frames (c, slot_frame (c, s), c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
+    int rc = slot_launch_shade (c, s, shade_from, up_to);
+    if (rc != MIBAYER_OK)
+      return rc;
+    rc = launch_frames (c, slot_frame (c, s), c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
     if (b == nb - 1) {          /* every row is on the device: the statistics once over the whole mosaic */
@@ -2619,6 +2891,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
   } else {
     Range r ("mibayer:kernel");
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_in, 0));
+    const int shade_rc = slot_launch_shade (c, s, 0, c->cfg.height);
+    if (shade_rc != MIBAYER_OK)
+      return shade_rc;
     const int rc = launch_frames (c, slot_frame (c, s), c->s_compute, 0, -1, c->colour ? &s.stage : nullptr);
     if (rc != MIBAYER_OK)
       return rc;
@@ -2661,8 +2936,9 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   if (rc != MIBAYER_OK)
     return rc;
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
-  /* (the captured graphs hold the demosaic launch only: a frame with statistics is launched without them) */
-  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on;
+  /* (the captured graphs hold the demosaic launch only: a frame with statistics or shading is launched without them) */
+  const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on
+      && !s.shade;
   /* bands pay when this frame has the link to itself (measured at 4K: +7 %
    * synchronous, -6 % with three frames in flight, which overlap anyway) */
   if (want_graph && c->graph_mode == 1

@@ -355,6 +355,35 @@ struct HistParams {
 /* one launch over `nframes` frames; p.hist must have been zeroed on the stream before */
 hipError_t launch_hist (const HistParams &p, int nframes, hipStream_t stream);
 
+/* Lens shading correction (mosaic_shade_kernel; include/mibayer.h, group `shading`): a pointwise pass over the mosaic,
+ * in place or into a second mosaic of the same sample format, one kernel per sample width, both byte orders */
+constexpr int kShadeAhead = 8;          /* dword loads in flight per lane = depth of the row loop; even */
+constexpr int kShadeMaxRows = 64;       /* rows a workgroup walks at most, even */
+constexpr int kShadeMinRows = 16;       /* ... and at least, when the launch is too small to fill the device otherwise */
+constexpr int kShadeSpread = 1024;      /* workgroups a launch is spread over before the rows per workgroup grow */
+constexpr int kShadeMaxNodes = 129;     /* per direction */
+struct ShadeParams {
+  const uint8_t *src;
+  uint8_t *dst;                 /* may be src */
+  unsigned long long src_frame_bytes, dst_frame_bytes;
+  const uint16_t *table;        /* device memory: [site 4][ny][nx], Q12 */
+  int width, height, src_stride, dst_stride;
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a dword: identity or a byte swap per 16-bit word (its own inverse) */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  int vmax;                     /* 2^depth - 1 */
+  int kx, ky;                   /* log2 of a cell's width / height, 2 .. 8 */
+  int nx, ny;                   /* nodes per row / column of a site's plane */
+  int black[4];                 /* per site */
+  int y0, y1;                   /* rows [y0, y1) */
+  /* filled by launch_shade */
+  int row_dwords;               /* dwords of a row that hold columns < width (the last one may hold two columns past it) */
+  int seg_rows;                 /* rows a workgroup walks, even */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row */
+};
+/* one launch over rows [p.y0, p.y1) of `nframes` frames */
+hipError_t launch_shade (const ShadeParams &p, int nframes, hipStream_t stream);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

@@ -2515,6 +2515,152 @@ hipError_t launch_hist (const HistParams &p, int nframes, hipStream_t stream)
 }
 
 /* ------------------------------------------------------------------------- */
+/* lens shading correction                                                     */
+/* ------------------------------------------------------------------------- */
+/* out = clamp (black + (((S - black) G + 2048) >> 12), 0, max) with the gain G interpolated bilinearly, per CFA site,
+ * from a grid of Q12 nodes (include/mibayer.h, group `shading`).  Pointwise: a lane reads a dword and writes the same
+ * dword, so source and destination may be one mosaic.  A workgroup is four waves side by side, each on a strip of 64
+ * dwords, walking seg_rows rows with kShadeAhead dword loads in flight per lane.  A cell is at least 4 pixels wide and
+ * starts on a multiple of 4, so the samples of a dword share their cell column: the lane's horizontal weights are fixed,
+ * and it keeps, per row parity and sample, the two node rows around the current cell row interpolated horizontally
+ * (a[], b[]: at most 32767 * 256 < 2^23).  A row then costs two multiply-adds per sample for G (< 2^31 + rounding, exact
+ * in uint32) and one for the sample.  The walk goes cell row by cell row: at a seam -- uniform over the workgroup -- the
+ * lower node row becomes the upper one and one new row of nodes is read (2 x 4 gathered 16-bit loads, cached).  Segments
+ * and cell rows start on even rows and kShadeAhead is even: the row parity inside the unrolled loop is that of i. */
+template <bool IN8>
+__global__ void __launch_bounds__ (256)
+mosaic_shade_kernel (ShadeParams p)
+{
+  constexpr int NS = IN8 ? 4 : 2;       /* samples of a dword */
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int ya = (p.y0 & ~1) + (int) blockIdx.y * p.seg_rows;   /* even; < y1 (launch_shade) */
+  const int yb = ya + p.seg_rows < p.y1 ? ya + p.seg_rows : p.y1;
+  const int g = (int) (strip * 256u + threadIdx.x);             /* dword of the row */
+  if (g >= p.row_dwords)
+    return;
+  const int x0 = IN8 ? 4 * g : 2 * g;                           /* its first column: even, < width */
+  const bool tail = IN8 && x0 + 2 >= p.width;                   /* columns x0 + 2, x0 + 3 are past the row's end */
+  const bool in_place = (const uint8_t *) p.dst == p.src;
+  const uint32_t cw = 1u << p.kx, ch = 1u << p.ky;
+  const int sh = p.kx + p.ky;
+  const uint32_t rnd = 1u << (sh - 1);
+  uint32_t wl[NS], wr[NS];
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    wr[k] = (uint32_t) (x0 + k) & (cw - 1u);
+    wl[k] = cw - wr[k];
+  }
+  /* node row jr of the four site planes, at the lane's cell column and the one right of it (ci + 1 <= nx - 1) */
+  const uint16_t *tab = p.table + (x0 >> p.kx);
+  auto node_row = [&] (int jr, uint32_t (&h)[2][NS]) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      const uint16_t *n = tab + ((size_t) s * (size_t) p.ny + (size_t) jr) * (size_t) p.nx;
+      const uint32_t l = n[0], r = n[1];
+#pragma unroll
+      for (int k = s & 1; k < NS; k += 2)
+        h[s >> 1][k] = l * wl[k] + r * wr[k];
+    }
+  };
+  const uint8_t *scol = p.src + frame * p.src_frame_bytes + 4 * (size_t) g;
+  uint8_t *dcol = p.dst + frame * p.dst_frame_bytes + 4 * (size_t) g;
+  int j = ya >> p.ky;                   /* j + 1 <= ny - 1 (launch_shade) */
+  uint32_t a[2][NS], b[2][NS];
+  node_row (j, a);
+  node_row (j + 1, b);
+  for (int y = ya; y < yb;) {           /* uniform over the workgroup; y is even here */
+    if ((y >> p.ky) != j) {             /* a cell-row seam */
+      j = y >> p.ky;
+#pragma unroll
+      for (int k = 0; k < NS; k++) {
+        a[0][k] = b[0][k];
+        a[1][k] = b[1][k];
+      }
+      node_row (j + 1, b);
+    }
+    const int seam = (j + 1) << p.ky;
+    const int ye = seam < yb ? seam : yb;
+    for (int yy = y; yy < ye; yy += kShadeAhead) {
+      const uint32_t fy0 = (uint32_t) yy & (ch - 1u);
+      uint32_t d[kShadeAhead];
+#pragma unroll
+      for (int i = 0; i < kShadeAhead; i++)
+        d[i] = yy + i < ye
+            ? __builtin_nontemporal_load ((const uint32_t *) (scol + (size_t) (yy + i) * (size_t) p.src_stride)) : 0u;
+#pragma unroll
+      for (int i = 0; i < kShadeAhead; i++) {
+        if (yy + i >= ye)
+          break;
+        if (yy + i < p.y0)              /* the row under an odd y0 */
+          continue;
+        const uint32_t fy = fy0 + (uint32_t) i;         /* < ch: the rows up to ye lie in cell row j */
+        uint32_t v[NS];
+        if (IN8) {
+#pragma unroll
+          for (int k = 0; k < NS; k++)
+            v[k] = (d[i] >> (8 * k)) & 0xffu;
+        } else {
+          const uint32_t m = __builtin_amdgcn_perm (d[i], d[i], p.in_sel) & p.mask2;
+          v[0] = m & 0xffffu;
+          v[NS - 1] = m >> 16;
+        }
+        uint32_t o = 0;
+#pragma unroll
+        for (int k = 0; k < NS; k++) {
+          const uint32_t gain = (a[i & 1][k] * (ch - fy) + b[i & 1][k] * fy + rnd) >> sh;       /* <= 32767 */
+          const int bl = p.black[2 * (i & 1) + (k & 1)];
+          int q = bl + ((((int) v[k] - bl) * (int) gain + 2048) >> 12);
+          q = q < 0 ? 0 : q > p.vmax ? p.vmax : q;
+          o |= (uint32_t) q << ((IN8 ? 8 : 16) * k);
+        }
+        if (!IN8)
+          o = __builtin_amdgcn_perm (o, o, p.in_sel);
+        uint8_t *out = dcol + (size_t) (yy + i) * (size_t) p.dst_stride;
+        if (tail)
+          *(uint16_t *) out = (uint16_t) o;
+        else if (in_place)
+          *(uint32_t *) out = o;
+        else
+          __builtin_nontemporal_store (o, (uint32_t *) out);
+      }
+    }
+    y = ye;
+  }
+}
+
+hipError_t launch_shade (const ShadeParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.width < 2 || (p.width & 1) || p.kx < 2 || p.kx > 8 || p.ky < 2 || p.ky > 8 || p.y0 < 0 || p.y1 <= p.y0
+      || p.y1 > p.height || p.nx < ((p.width - 1) >> p.kx) + 2 || p.ny < ((p.height - 1) >> p.ky) + 2 || !p.table)
+    return hipErrorInvalidValue;        /* (a node past the table, a cell narrower than a dword) */
+  ShadeParams q = p;
+  q.row_dwords = p.in8 ? (p.width + 3) / 4 : p.width / 2;
+  const long long strips = (q.row_dwords + 255) / 256;
+  /* rows per workgroup: as many as kShadeMaxRows, cut finer (one frame on the host path, one band of it) until the
+   * launch has kShadeSpread workgroups */
+  const long long h = p.y1 - (p.y0 & ~1);
+  long long rows = h * strips * nframes / kShadeSpread;
+  rows = rows < kShadeMinRows ? kShadeMinRows : rows > kShadeMaxRows ? kShadeMaxRows : rows;
+  if ((h + rows - 1) / rows > 65535)
+    rows = (h + 65534) / 65535;
+  rows = (rows + 1) & ~1LL;
+  const long long gy = (h + rows - 1) / rows;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535)
+    return hipErrorInvalidValue;
+  q.seg_rows = (int) rows;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  const dim3 grid ((unsigned) (strips * nframes), (unsigned) gy);
+  if (p.in8)
+    hipLaunchKernelGGL (mosaic_shade_kernel<true>, grid, dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL (mosaic_shade_kernel<false>, grid, dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

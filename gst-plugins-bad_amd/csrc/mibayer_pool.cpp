@@ -62,6 +62,8 @@
 /* ... and the histogram's: mibayer_pool_set_hist is refused there too */
 #pragma weak mibayer_set_hist
 #pragma weak mibayer_frame_hist
+/* ... and the shading table's: mibayer_pool_set_shading is refused there too */
+#pragma weak mibayer_set_shading
 
 #include <sched.h>
 
@@ -85,6 +87,11 @@ struct StatsGrid {
   int zones_x, zones_y;         /* (0, 0): no zones */
   uint32_t lo, hi;
   int hist, x0, y0, w, h;       /* hist = 0: no histogram */
+};
+/* what mibayer_pool_set_shading asked for: the parameters and the pool's copy of the table (par.table points into it) */
+struct ShadeSet {
+  mibayer_shading par;
+  std::vector<uint16_t> table;
 };
 /* a frame's histogram rides behind its zones in the same vector, as it does in a context's slot */
 constexpr size_t kHistZones = sizeof (mibayer_hist) / sizeof (mibayer_stats_zone);
@@ -117,6 +124,8 @@ struct Frame {
    * and the frame's zones, fetched from the context by the thread that retired the frame there */
   std::shared_ptr<const StatsGrid> grid;
   std::vector<mibayer_stats_zone> zones;
+  /* mibayer_pool_set_shading: the table the pool held when the frame was accepted (NULL: none), applied like the stage */
+  std::shared_ptr<const ShadeSet> shade;
 };
 
 struct Shard {
@@ -131,6 +140,7 @@ struct Shard {
   std::shared_ptr<const mibayer_colour> applied;        /* the stage its context holds (touched by whichever ONE
                                                            thread hands frames to the context) */
   std::shared_ptr<const StatsGrid> applied_grid;        /* ... and the statistics grid (NULL: off, as created) */
+  std::shared_ptr<const ShadeSet> applied_shade;        /* ... and the shading table (NULL: off, as created) */
   std::atomic<long long> completions { 0 };
   std::atomic<long long> fail_after { -1 };     /* fault injection; -1 = never */
   /* helper thread */
@@ -168,9 +178,22 @@ void apply_colour (Shard *sh, const Frame *f)
     sh->applied = f->colour;
 }
 
-/* the same for the frame's statistics grid */
+/* the same for the frame's shading table: a frame converted again on another shard is shaded there with its own.
+ * mibayer_pool_set_shading has checked the table by the context's own rules, so what can fail here is the device
+ * (allocation, upload).  As with the stage, the frame is then converted with what the context holds, and the table is
+ * tried again with the next frame; a device that is really gone fails the frame's submit and is dropped there. */
+void apply_shading (Shard *sh, const Frame *f)
+{
+  if (f->shade == sh->applied_shade || !mibayer_set_shading)
+    return;
+  if (mibayer_set_shading (sh->ctx, f->shade ? &f->shade->par : NULL) == MIBAYER_OK)
+    sh->applied_shade = f->shade;
+}
+
+/* the same for the frame's statistics grid (and, with it, the shading table: the two travel together) */
 void apply_stats (Shard *sh, const Frame *f)
 {
+  apply_shading (sh, f);
   if (f->grid == sh->applied_grid || !mibayer_set_stats)
     return;
   const StatsGrid off = {};
@@ -379,6 +402,7 @@ struct mibayer_pool {
   std::vector<mibayer_stats_zone> last_zones;
   bool has_zones = false;
   std::shared_ptr<const StatsGrid> last_grid;   /* ... which says what last_zones holds */
+  std::shared_ptr<const ShadeSet> shade;        /* mibayer_pool_set_shading: the table of the frames submitted from now on */
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -808,6 +832,42 @@ extern "C" int mibayer_pool_frame_hist (mibayer_pool *pool, mibayer_hist *out)
   return MIBAYER_OK;
 }
 
+/* The shading table of the frames submitted from now on: kept with each frame and applied like the colour stage
+ * (apply_shading).  The rules are the context layer's (include/mibayer.h), restated on the resolved configuration so
+ * that a bad table is refused here and not frames later. */
+extern "C" int mibayer_pool_set_shading (mibayer_pool *pool, const mibayer_shading *shading)
+{
+  if (!pool || !mibayer_set_shading)
+    return MIBAYER_ERR_ARG;
+  if (!shading) {
+    pool->shade.reset ();
+    return MIBAYER_OK;
+  }
+  mibayer_cfg f;
+  if (mibayer_get_cfg (pool->shards[0]->ctx, &f) != MIBAYER_OK || (f.flags & MIBAYER_FLAG_RGB2BAYER)
+      || shading->struct_size != sizeof (mibayer_shading) || !shading->table || shading->cell_log2_x < 2
+      || shading->cell_log2_x > 8 || shading->cell_log2_y < 2 || shading->cell_log2_y > 8)
+    return MIBAYER_ERR_ARG;
+  const int nx = ((f.width - 1) >> shading->cell_log2_x) + 2, ny = ((f.height - 1) >> shading->cell_log2_y) + 2;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
+  if (nx > MIBAYER_SHADING_MAX_NODES || ny > MIBAYER_SHADING_MAX_NODES)
+    return MIBAYER_ERR_ARG;
+  for (int s = 0; s < 4; s++)
+    if (shading->black[s] > vmax)
+      return MIBAYER_ERR_ARG;
+  const size_t n = (size_t) 4 * (size_t) ny * (size_t) nx;
+  for (size_t e = 0; e < n; e++)
+    if (shading->table[e] > 32767)
+      return MIBAYER_ERR_ARG;
+  auto set = std::make_shared<ShadeSet> ();
+  set->table.assign (shading->table, shading->table + n);
+  set->par = *shading;
+  set->par.table = set->table.data ();
+  pool->shade = set;
+  return MIBAYER_OK;
+}
+
 extern "C" int mibayer_pool_inject_stall (mibayer_pool *pool, int shard, int ms)
 {
   if (!pool || shard < 0 || shard >= (int) pool->shards.size ())
@@ -895,7 +955,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       sh->stall_ms = 0;
       (void) mibayer_internal_stall (sh->ctx, ms);
     }
-    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {} };
+    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {}, pool->shade };
     if (pool->use_helpers && (mibayer_internal_is_pageable (src) || mibayer_internal_is_pageable (dst))
         && !sh->pageable_seen) {
       sh->pageable_seen = true;

@@ -81,8 +81,13 @@ enum
   PROP_TIMEOUT_MS,
   PROP_METHOD,
   PROP_COLOUR_FIRST,            /* GST_MI_COLOUR_N_PROPS ids (gstmicolour.h) */
-  PROP_COLOUR_LAST = PROP_COLOUR_FIRST + GST_MI_COLOUR_N_PROPS - 1
+  PROP_COLOUR_LAST = PROP_COLOUR_FIRST + GST_MI_COLOUR_N_PROPS - 1,
+  PROP_SHADING_FILE
 };
+
+/* bound weakly, like the colour stage's entry points (gstmicolour.h): over a libmibayer without lens shading
+ * correction a shading-file is an element error */
+#pragma weak mibayer_pool_set_shading
 
 #define DEFAULT_DEVICE_ID 0
 #define DEFAULT_INFLIGHT 1
@@ -440,6 +445,71 @@ element_mosaic_stride (GstMiBayerElement * self)
       : GST_ROUND_UP_4 (self->width);
 }
 
+/* shading-file: reads the table, checks it against the negotiated size and hands it to the pool; NULL, or why not
+ * (a string the caller owns) */
+static gchar *
+element_load_shading (GstMiBayerElement * self)
+{
+  enum { HEADER = 4 + 9 * 4 };
+  gchar *data = NULL, *why = NULL;
+  gsize len = 0;
+  GError *err = NULL;
+  mibayer_shading sh;
+  guint32 version, nx, ny, want_nx, want_ny;
+  guint16 *table = NULL;
+  gsize n, e;
+  int rc;
+
+  if (!mibayer_pool_set_shading)
+    return g_strdup ("this libmibayer has no lens shading correction");
+  if (!g_file_get_contents (self->act.shading_file, &data, &len, &err)) {
+    why = g_strdup (err->message);
+    g_clear_error (&err);
+    return why;
+  }
+  if (len < HEADER || memcmp (data, "MISH", 4) != 0) {
+    why = g_strdup ("not a MISH file");
+    goto done;
+  }
+  version = GST_READ_UINT32_LE (data + 4);
+  memset (&sh, 0, sizeof sh);
+  sh.struct_size = sizeof sh;
+  sh.cell_log2_x = (gint32) GST_READ_UINT32_LE (data + 8);
+  sh.cell_log2_y = (gint32) GST_READ_UINT32_LE (data + 12);
+  nx = GST_READ_UINT32_LE (data + 16);
+  ny = GST_READ_UINT32_LE (data + 20);
+  for (e = 0; e < 4; e++)
+    sh.black[e] = GST_READ_UINT32_LE (data + 24 + 4 * e);
+  if (version != 1 || sh.cell_log2_x < 2 || sh.cell_log2_x > 8 || sh.cell_log2_y < 2 || sh.cell_log2_y > 8) {
+    why = g_strdup_printf ("version %u, cells of 2^%d x 2^%d: not supported", version, sh.cell_log2_x, sh.cell_log2_y);
+    goto done;
+  }
+  want_nx = (guint32) ((self->width - 1) >> sh.cell_log2_x) + 2;
+  want_ny = (guint32) ((self->height - 1) >> sh.cell_log2_y) + 2;
+  if (nx != want_nx || ny != want_ny) {
+    why = g_strdup_printf ("the table has %u x %u nodes, a %dx%d frame needs %u x %u", nx, ny, self->width,
+        self->height, want_nx, want_ny);
+    goto done;
+  }
+  n = (gsize) 4 * ny * nx;
+  if (len != HEADER + 2 * n) {
+    why = g_strdup_printf ("%" G_GSIZE_FORMAT " bytes, %u x %u nodes need %" G_GSIZE_FORMAT, len, nx, ny,
+        (gsize) HEADER + 2 * n);
+    goto done;
+  }
+  table = g_new (guint16, n);
+  for (e = 0; e < n; e++)
+    table[e] = GST_READ_UINT16_LE (data + HEADER + 2 * e);
+  sh.table = table;
+  rc = mibayer_pool_set_shading (self->pool, &sh);
+  if (rc != MIBAYER_OK)
+    why = g_strdup_printf ("mibayer_pool_set_shading: %s", mibayer_strerror (rc));
+done:
+  g_free (table);
+  g_free (data);
+  return why;
+}
+
 /* `video_stride` is the mapped stride of the 4-byte-per-pixel frame (8 bytes
  * for ARGB64): the destination stride of bayer2rgb (reference
  * gstbayer2rgb.c:476), the source stride of rgb2bayer (gstrgb2bayer.c:256).
@@ -559,6 +629,17 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
         g_strdup_printf ("mibayer_pool_set_colour: %s", mibayer_strerror (rc)));
     return FALSE;
   }
+  if (!inverse && self->act.shading_file && self->act.shading_file[0]) {
+    gchar *why = element_load_shading (self);
+
+    if (why) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up shading-file=\"%s\"", LABEL (self), self->act.shading_file), why);
+      return FALSE;
+    }
+  }
   if (want_colour && ((GstMiColourProps *) self->act.colour)->white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD) {
     guint32 lo, hi;
 
@@ -645,6 +726,10 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
     case PROP_METHOD:
       self->method = g_value_get_enum (value);
       break;
+    case PROP_SHADING_FILE:
+      g_free (self->shading_file);
+      self->shading_file = g_value_dup_string (value);
+      break;
     default:
       if (gst_mi_colour_set_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -683,6 +768,9 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
     case PROP_METHOD:
       g_value_set_enum (value, self->method);
       break;
+    case PROP_SHADING_FILE:
+      g_value_set_string (value, self->shading_file ? self->shading_file : "");
+      break;
     default:
       if (gst_mi_colour_get_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -704,6 +792,9 @@ element_finalize (GObject * object)
   self->act.devices = NULL;
   g_free (self->failure_note);
   self->failure_note = NULL;
+  g_free (self->shading_file);
+  g_free (self->act.shading_file);
+  self->shading_file = self->act.shading_file = NULL;
   if (self->colour) {
     gst_mi_colour_props_clear (self->colour);
     gst_mi_colour_props_clear (self->act.colour);
@@ -1261,6 +1352,8 @@ element_start (GstBaseTransform * base)
   self->act.pinned_pool = self->pinned_pool;
   self->act.timeout_ms = self->timeout_ms;
   self->act.method = self->method;
+  g_free (self->act.shading_file);
+  self->act.shading_file = g_strdup (self->shading_file);
   gst_mi_colour_props_copy (self->act.colour, self->colour);
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
@@ -1346,6 +1439,16 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             G_PARAM_STATIC_STRINGS));
   if (!inverse)
     gst_mi_colour_install_properties (object_class, PROP_COLOUR_FIRST);
+  if (!inverse)
+    g_object_class_install_property (object_class, PROP_SHADING_FILE,
+        g_param_spec_string ("shading-file", "Lens shading table",
+            "File with the lens shading correction applied to the mosaic before "
+            "the demosaic: little-endian \"MISH\", u32 version = 1, cell log2 x, "
+            "cell log2 y, nodes x, nodes y, black level per CFA site [4], then "
+            "4 * ny * nx Q12 gains (u16, site-major; tools/shading_calibrate.py "
+            "writes one); must fit the negotiated size; empty = off", "",
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
   transform_class->get_unit_size = GST_DEBUG_FUNCPTR (element_get_unit_size);

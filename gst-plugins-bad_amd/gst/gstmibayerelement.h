@@ -61,6 +61,7 @@ struct _GstMiBayerElement
   gint timeout_ms;              /* deadline of every wait for a GPU; 0 = none */
   gint method;                  /* GstMiBayerMethod (bayer2rgb only) */
   gpointer colour;              /* GstMiColourProps* (gstmicolour.h; bayer2rgb only): the colour-stage properties */
+  gchar *shading_file;          /* lens shading table (bayer2rgb only); NULL or "" = off */
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -74,6 +75,7 @@ struct _GstMiBayerElement
     gint timeout_ms;
     gint method;
     gpointer colour;            /* GstMiColourProps* */
+    gchar *shading_file;
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;

@@ -72,6 +72,8 @@ extern "C" {
  * point was added, and a cfg without the flag means what it meant. */
 /* 5, later additive: planar 8-bit output -- MIBAYER_FLAG_DST_PLANAR, a sixth deep flag; no struct field and no entry
  * point was added, and a cfg without the flag means what it meant. */
+/* 5, later additive: lens shading correction -- struct mibayer_shading and the entry points of group `shading`; a
+ * context without a table converts what it converted. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -106,6 +108,10 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group shading: lens shading correction -- a per-site gain grid applied to the mosaic before everything else reads it,
+ *   and the helper that turns flat-field zone statistics into such a grid
+ *     mibayer_shading_nodes mibayer_set_shading mibayer_get_shading mibayer_shade_device mibayer_pool_set_shading
+ *     mibayer_stats_shading
  * group hist: the other half of the ISP statistics block -- a 256-bin histogram per CFA site of the mosaic, and the
  *   percentile and auto-exposure helpers that read it
  *     mibayer_hist_device mibayer_set_hist mibayer_frame_hist mibayer_pool_set_hist mibayer_pool_frame_hist
@@ -453,6 +459,88 @@ int mibayer_hist_percentile (const mibayer_hist *hist, int pattern, int colour, 
  * fraction, depth outside {8, 10, 12, 14, 16}, target outside (0, 1] or max_gain outside [1, 15.99]. */
 int mibayer_hist_exposure (const mibayer_hist *hist, int pattern, int depth, const double black[3],
     const double gains[3], double fraction, double target, double max_gain, double *exposure);
+
+/* ---- lens shading correction (additive within version 5: a struct and the entry points of group `shading`) ------ */
+
+/* Vignetting and colour shading: a gain per CFA site that varies smoothly over the frame, applied to the MOSAIC by a
+ * pointwise kernel before the demosaic, the statistics and the histogram read it.  Integers only, bit-exact.
+ *   sample   S, depth, max = 2^depth - 1 and site s = 2 (y & 1) + (x & 1) exactly as in group `stats`: the byte of an
+ *            8-bit mosaic, or the 16-bit word in the context's byte order masked to `bits`
+ *   grid     cells of cw = 1 << kx by ch = 1 << ky pixels, kx and ky in 2 .. 8; nodes nx = ((W - 1) >> kx) + 2,
+ *            ny = ((H - 1) >> ky) + 2; more than 129 nodes in a direction: MIBAYER_ERR_ARG.  The table is
+ *            uint16_t g[4][ny][nx], site-major, Q12 (4096 = 1.0), every entry in 0 .. 32767 (above: MIBAYER_ERR_ARG)
+ *   gain     at (x, y), with g = the plane of the pixel's site: i = x >> kx, fx = x & (cw - 1), j = y >> ky,
+ *            fy = y & (ch - 1),
+ *              G = ((g[j][i] (cw - fx) + g[j][i+1] fx) (ch - fy) + (g[j+1][i] (cw - fx) + g[j+1][i+1] fx) fy
+ *                   + (1 << (kx + ky - 1))) >> (kx + ky)                  exact in uint32: 32767 * 2^16 < 2^32
+ *   apply    black[4] per site, each <= max (else MIBAYER_ERR_ARG):  d = S - black[s]  (signed),
+ *              out = clamp (black[s] + ((d G + 2048) >> 12), 0, max)      arithmetic shift; d G + 2048 fits int32
+ *            a deep sample is written as the 16-bit word in the source's byte order with the bits above `bits` zero.
+ *            Only the first W samples of a row are written: the stride padding of an out-of-place destination keeps
+ *            what it held.
+ * An all-4096 table is the identity on the masked samples, whatever the black levels. */
+typedef struct mibayer_shading {
+  uint32_t struct_size;         /* = sizeof (mibayer_shading) */
+  int32_t cell_log2_x;          /* kx */
+  int32_t cell_log2_y;          /* ky */
+  uint32_t black[4];            /* per site, at native depth */
+  const uint16_t *table;        /* host memory, 4 * ny * nx entries; copied */
+} mibayer_shading;
+#define MIBAYER_SHADING_MAX_NODES 129   /* per direction */
+
+/* nodes of a width x height frame under cells of (1 << kx) x (1 << ky) (pure host code).  MIBAYER_ERR_ARG for a NULL
+ * pointer, width or height < 1, kx or ky outside 2 .. 8, or more than MIBAYER_SHADING_MAX_NODES in a direction. */
+int mibayer_shading_nodes (int width, int height, int kx, int ky, int *nx, int *ny);
+/* Sets the table of a context (NULL: off, the default).  Valid on every bayer2rgb context (8-bit, deep, MHC, COLOUR,
+ * 24-bit, planar); MIBAYER_ERR_ARG on an RGB2BAYER context, a bad struct_size, a NULL table and on values outside the
+ * rules above.  The table is copied into device memory of the context before the call returns.  It applies to the
+ * frames accepted (mibayer_submit / mibayer_process_host) and the mibayer_shade_device calls made after it returns;
+ * frames already accepted keep the table they were accepted with.  May be called between frames, from any thread.
+ * HOST PATH: while a table is set, every accepted frame is shaded in place on the device copy of the mosaic that its
+ * ring slot holds, each row exactly once (band by band when the frame is launched in bands), before anything else
+ * reads it: the demosaic, the statistics and the histogram of the frame see corrected samples.  While a table is set a
+ * MIBAYER_FLAG_HIPGRAPH context launches without graphs.  With no table the bytes are those of the same context
+ * before this entry point existed.  mibayer_process_device[_list] never shades: its source is const.
+ * mibayer_get_shading: out->table = NULL and returns MIBAYER_ERR_EMPTY when none is set; else the parameters, with
+ * out->table pointing at the context's host copy (valid until the next mibayer_set_shading / mibayer_destroy). */
+int mibayer_set_shading (mibayer_ctx *ctx, const mibayer_shading *shading);
+int mibayer_get_shading (const mibayer_ctx *ctx, mibayer_shading *out);
+/* Device path: ONE launch shading `nframes` mosaics with the table set before, frame f read at d_src + f *
+ * src_frame_bytes (rows of cfg.src_stride bytes) and written at d_dst + f * dst_frame_bytes in the same layout;
+ * d_dst == d_src is allowed: every sample is read and written by the same lane.  In place the two pitches must be
+ * equal (nframes > 1 with d_dst == d_src and dst_frame_bytes != src_frame_bytes: MIBAYER_ERR_GEOMETRY); a destination
+ * that overlaps the source in any other way is undefined.  Errors follow
+ * mibayer_stats_device: MIBAYER_ERR_ARG on an RGB2BAYER context, a NULL pointer, nframes < 0, a pointer that is not a
+ * multiple of 4; MIBAYER_ERR_GEOMETRY for a frame pitch (of either side) as in mibayer_process_device;
+ * MIBAYER_ERR_EMPTY when no table is set.  Covered by mibayer_sync when launched on the context's stream. */
+int mibayer_shade_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream);
+/* ... of a pool: the table of the frames mibayer_pool_submit accepts after it returns (NULL: off).  The pool keeps the
+ * table with each frame, like the colour stage, and hands it to a shard's context together with the frame: a frame
+ * converted again on another shard after a failover is shaded there, from its host copy, with the table it was
+ * submitted with.  Call it from the thread that calls mibayer_pool_submit. */
+int mibayer_pool_set_shading (mibayer_pool *pool, const mibayer_shading *shading);
+/* A table from the zone statistics of a FLAT FIELD (pure host code, doubles, in exactly this order; no fused
+ * multiply-add).  zones: zones_y x zones_x of a width x height frame (mibayer_stats_device / mibayer_frame_stats);
+ * zcw, zch = the pixels and rows of a zone as in group `stats`; ux = ceil (W / zcw), uy = ceil (H / zch) zones per
+ * direction hold pixels, the others are ignored.  Centre of zone column a: cx[a] = (a zcw + min ((a + 1) zcw, W)) * 0.5,
+ * of zone row b: cy[b] likewise with zch and H.  Per site s:
+ *   1. m[b][a] = (double) sum[s] / (double) count[s] - (double) black[s] for a zone with count[s] > 0; an empty zone
+ *      takes m of the non-empty zone (a', b') with the smallest (a' - a)^2 + (b' - b)^2, the first in row-major order
+ *      among equals.  No non-empty zone: all of table_out = 4096, returns 0.
+ *   2. node (j, i) lies at px = (double) (i << kx), py = (double) (j << ky).  Along x: px <= cx[0] (or ux == 1): a = 0,
+ *      tx = 0; px >= cx[ux-1]: a = ux - 1, tx = 0; else a = the largest index with cx[a] <= px and
+ *      tx = (px - cx[a]) / (cx[a+1] - cx[a]); a1 = min (a + 1, ux - 1).  Along y alike: b, ty, b1.
+ *        top = m[b][a] + (m[b][a1] - m[b][a]) * tx,  bot = m[b1][a] + (m[b1][a1] - m[b1][a]) * tx,
+ *        v[j][i] = top + (bot - top) * ty
+ *      Any v that is not > 0: all of table_out = 4096, returns 0.
+ *   3. vmax = the largest v of the site; gain = vmax / v[j][i], clamped to [1, max_gain];
+ *      g[s][j][i] = (uint16_t) floor (gain * 4096 + 0.5).
+ * Returns 1.  black NULL = 0.  MIBAYER_ERR_ARG for a NULL zones or table_out, a zone grid outside the rule of group
+ * `stats`, width < 2 or odd, height < 1, a grid as in mibayer_shading_nodes, or max_gain outside [1, 7.99] (NaN
+ * included). */
+int mibayer_stats_shading (const mibayer_stats_zone *zones, int zones_x, int zones_y, int width, int height,
+    const uint32_t black[4], int kx, int ky, double max_gain, uint16_t *table_out);
 
 /* ---- global ------------------------------------------------------------- */
 
