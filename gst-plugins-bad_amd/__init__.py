@@ -222,6 +222,25 @@ def stats_shading(zones, width, height, black, kx, ky, max_gain):
     return rc, out
 
 
+DPC_MAX_DEFECTS = 65536
+
+
+class Dpc(ctypes.Structure):
+    """struct mibayer_dpc (include/mibayer.h): the hot and cold thresholds (-1 = off) and the list of known defects,
+    (n, 2) of (x, y) in host memory (the library copies it).  Dpc(hot, cold, defects) keeps the array alive as long as
+    the structure lives."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("hot", ctypes.c_int32), ("cold", ctypes.c_int32),
+                ("ndefects", ctypes.c_uint32), ("defects", ctypes.c_void_p)]
+
+    def __init__(self, hot=-1, cold=-1, defects=None):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(Dpc)
+        self.hot, self.cold = int(hot), int(cold)
+        self._list = None if defects is None else np.ascontiguousarray(defects, np.uint32).reshape(-1, 2)
+        self.ndefects = 0 if defects is None else len(self._list)
+        self.defects = None if defects is None or not len(self._list) else self._list.ctypes.data
+
+
 HIST_BINS = 256
 
 
@@ -406,6 +425,10 @@ ABI = {
     "mibayer_get_shading": (ctypes.c_int, [_vp, ctypes.POINTER(Shading)]),
     "mibayer_shade_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
     "mibayer_pool_set_shading": (ctypes.c_int, [_vp, ctypes.POINTER(Shading)]),
+    "mibayer_set_dpc": (ctypes.c_int, [_vp, ctypes.POINTER(Dpc)]),
+    "mibayer_get_dpc": (ctypes.c_int, [_vp, ctypes.POINTER(Dpc)]),
+    "mibayer_dpc_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "mibayer_pool_set_dpc": (ctypes.c_int, [_vp, ctypes.POINTER(Dpc)]),
     "mibayer_stats_shading": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int,
                                              ctypes.c_double, _vp]),
@@ -565,6 +588,11 @@ class Pool:
         _check(lib().mibayer_pool_set_shading(self._h, None if shading is None else ctypes.byref(shading)),
                "mibayer_pool_set_shading")
 
+    def set_dpc(self, dpc):
+        """mibayer_pool_set_dpc: the defective pixel correction (a Dpc, or None = off) of the frames submitted from
+        now on"""
+        _check(lib().mibayer_pool_set_dpc(self._h, None if dpc is None else ctypes.byref(dpc)), "mibayer_pool_set_dpc")
+
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_pool_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_pool_submit")
 
@@ -700,6 +728,31 @@ class Context:
         pitch = src_frame_bytes or self.src_bytes
         _check(lib().mibayer_shade_device(self._h, _vp(d_src), pitch, _vp(d_src if d_dst is None else d_dst),
                                           (dst_frame_bytes or pitch), nframes, _vp(s)), "mibayer_shade_device")
+
+    # -- defective pixel correction ---------------------------------------------------------
+    def set_dpc(self, dpc):
+        """mibayer_set_dpc: the correction (a Dpc, or None = off) of the host-path frames accepted and the dpc_device
+        calls made from now on"""
+        _check(lib().mibayer_set_dpc(self._h, None if dpc is None else ctypes.byref(dpc)), "mibayer_set_dpc")
+
+    def get_dpc(self):
+        """mibayer_get_dpc: None when off, else (hot, cold, (n, 2) uint32 list sorted by (y, x) without duplicates)"""
+        out = Dpc()
+        rc = lib().mibayer_get_dpc(self._h, ctypes.byref(out))
+        if rc == ERR_EMPTY:
+            return None
+        _check(rc, "mibayer_get_dpc")
+        if not out.ndefects:
+            return out.hot, out.cold, np.zeros((0, 2), np.uint32)
+        arr = np.ctypeslib.as_array(ctypes.cast(out.defects, ctypes.POINTER(ctypes.c_uint32)), (out.ndefects, 2)).copy()
+        return out.hot, out.cold, arr
+
+    def dpc_device(self, d_src, d_dst, nframes=1, src_frame_bytes=None, dst_frame_bytes=None, stream="ctx"):
+        """mibayer_dpc_device: nframes mosaics at d_src corrected into d_dst (never d_src) with the parameters set"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        pitch = src_frame_bytes or self.src_bytes
+        _check(lib().mibayer_dpc_device(self._h, _vp(d_src), pitch, _vp(d_dst), (dst_frame_bytes or pitch), nframes,
+                                        _vp(s)), "mibayer_dpc_device")
 
     # -- mosaic zone statistics -------------------------------------------------------------
     def stats_device(self, d_src, d_stats, zones_x, zones_y, lo, hi, nframes=1, src_frame_bytes=None, stream="ctx"):

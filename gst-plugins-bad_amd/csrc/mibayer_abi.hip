@@ -17,6 +17,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <limits.h>
 #include <math.h>
@@ -157,6 +158,16 @@ struct ShadeTable {
   ~ShadeTable ();
 };
 
+/* a defective pixel correction as set (mibayer_set_dpc): the parameters, the sorted host copy of the list and the
+ * device copy the list kernel reads */
+struct DpcSet {
+  mibayer_dpc par;              /* par.defects = host.data () */
+  int device = 0;
+  std::vector<uint32_t> host;   /* x, y pairs sorted by (y, x), no duplicates */
+  uint32_t *d_list = nullptr;
+  ~DpcSet ();
+};
+
 struct Slot {
   uint8_t *d_src = nullptr;
   uint8_t *d_dst = nullptr;
@@ -194,6 +205,10 @@ struct Slot {
   /* mibayer_set_shading: the table of the frame in the slot (NULL: none), taken when the frame is accepted like the
    * stage; the reference keeps its device copy alive while the frame's launches may read it */
   std::shared_ptr<const ShadeTable> shade;
+  /* mibayer_set_dpc: likewise.  While the frame in the slot is corrected its upload lands in d_raw, a second mosaic made
+   * when the slot first needs one, and the pass writes d_src */
+  std::shared_ptr<const DpcSet> dpc;
+  uint8_t *d_raw = nullptr;
 };
 
 int device_count_cached ()
@@ -347,6 +362,7 @@ struct mibayer_ctx {
   bool last_hist_on = false;
   mibayer_hist last_hist;
   std::shared_ptr<const ShadeTable> shading;    /* mibayer_set_shading (NULL: off), under stats_mu */
+  std::shared_ptr<const DpcSet> dpc;            /* mibayer_set_dpc (NULL: off), under stats_mu */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -1715,7 +1731,7 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
 {
   if (how == RELEASE_ORPHAN) {
     Wedge *w = c->wedge;
-    for (void *m : { (void *) s.d_src, (void *) s.d_dst, (void *) s.d_stats })
+    for (void *m : { (void *) s.d_src, (void *) s.d_dst, (void *) s.d_stats, (void *) s.d_raw })
       if (m)
         w->dev_mem.push_back (m);
     if (s.h_stats)
@@ -1751,6 +1767,8 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
   }
   if (s.d_stats)
     (void) hipFree (s.d_stats);
+  if (s.d_raw)
+    (void) hipFree (s.d_raw);
   if (s.h_stats)
     mibayer_host_free (s.h_stats);
   if (s.ev_in)
@@ -2238,14 +2256,23 @@ extern "C" int mibayer_frame_stats (mibayer_ctx *c, mibayer_stats_zone *out, int
 static int slot_take_stats (mibayer_ctx *c, Slot &s)
 {
   std::shared_ptr<const ShadeTable> shade;
+  std::shared_ptr<const DpcSet> dpc;
   {
     std::lock_guard<std::mutex> lk (c->stats_mu);
     s.grid = c->stats_grid;
     s.win = c->hist_win;
     shade = c->shading;
+    dpc = c->dpc;
   }
   s.shade.swap (shade);         /* the slot's old table may go here (hipFree waits for the device): outside the lock */
   shade.reset ();
+  s.dpc.swap (dpc);
+  dpc.reset ();
+  if (s.dpc && !s.d_raw && hip_failed (hipMalloc ((void **) &s.d_raw, c->src_bytes), "hipMalloc (dpc mosaic)")) {
+    s.d_raw = nullptr;
+    (void) hipGetLastError ();
+    return MIBAYER_ERR_NOMEM;
+  }
   if (s.grid.zones_x == 0 && !s.win.on)
     return MIBAYER_OK;
   if (!s.d_stats)
@@ -2580,6 +2607,163 @@ extern "C" int mibayer_stats_shading (const mibayer_stats_zone *zones, int zones
   return 1;
 }
 
+/* ---- defective pixel correction (group `dpc`) -------------------------------------------- */
+
+/* as ~ShadeTable: hipFree waits for the launches that read the list */
+DpcSet::~DpcSet ()
+{
+  if (!d_list || g_wedges_open.load () != 0)
+    return;
+  DeviceGuard guard (device);
+  if (guard.ok)
+    (void) hipFree (d_list);
+}
+
+extern "C" int mibayer_set_dpc (mibayer_ctx *c, const mibayer_dpc *d)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const DpcSet> next;
+  if (d) {
+    const int vmax = (int) sample_format (c->cfg).vmax;
+    if (d->struct_size != sizeof (mibayer_dpc) || d->hot < -1 || d->hot > vmax || d->cold < -1 || d->cold > vmax
+        || d->ndefects > MIBAYER_DPC_MAX_DEFECTS || (d->ndefects > 0 && !d->defects))
+      return MIBAYER_ERR_ARG;
+    const uint32_t w = (uint32_t) c->cfg.width, h = (uint32_t) c->cfg.height;
+    for (uint32_t e = 0; e < d->ndefects; e++)
+      if (d->defects[2 * e] >= w || d->defects[2 * e + 1] >= h)
+        return MIBAYER_ERR_ARG;
+    if (h < 4)
+      return MIBAYER_ERR_GEOMETRY;
+    std::shared_ptr<DpcSet> t (new (std::nothrow) DpcSet);
+    if (!t)
+      return MIBAYER_ERR_NOMEM;
+    /* sorted by (y, x) as one 64-bit key, duplicates dropped */
+    std::vector<uint64_t> keys (d->ndefects);
+    for (uint32_t e = 0; e < d->ndefects; e++)
+      keys[e] = ((uint64_t) d->defects[2 * e + 1] << 32) | d->defects[2 * e];
+    std::sort (keys.begin (), keys.end ());
+    keys.erase (std::unique (keys.begin (), keys.end ()), keys.end ());
+    for (uint64_t k : keys) {
+      t->host.push_back ((uint32_t) k);
+      t->host.push_back ((uint32_t) (k >> 32));
+    }
+    t->par = *d;
+    t->par.ndefects = (uint32_t) keys.size ();
+    t->par.defects = t->host.data ();
+    t->device = c->device;
+    if (!t->host.empty ()) {
+      DeviceGuard guard (c->device);
+      if (!guard.ok)
+        return MIBAYER_ERR_HIP;
+      HIP_TRY (hipMalloc ((void **) &t->d_list, t->host.size () * sizeof (uint32_t)));
+      HIP_TRY (hipMemcpy (t->d_list, t->host.data (), t->host.size () * sizeof (uint32_t), hipMemcpyHostToDevice));
+    }
+    next = t;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->dpc.swap (next);           /* the set replaced goes when the last frame that took it has gone */
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_get_dpc (const mibayer_ctx *c, mibayer_dpc *out)
+{
+  if (!c || !out || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (!c->dpc) {
+    memset (out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    out->hot = out->cold = -1;
+    return MIBAYER_ERR_EMPTY;
+  }
+  *out = c->dpc->par;
+  return MIBAYER_OK;
+}
+
+/* the kernels' arguments for set `t` on context `c`, rows [y0, y1): the listed defects of those rows by bisection */
+static void dpc_params (const mibayer_ctx *c, const DpcSet &t, int y0, int y1, DpcParams *q)
+{
+  const mibayer_cfg &f = c->cfg;
+  const SampleFormat sf = sample_format (f);
+  memset (q, 0, sizeof *q);
+  q->list = t.d_list;
+  const int n = (int) t.par.ndefects;
+  auto first_at = [&] (int y) {         /* the first entry of row y or below it */
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) / 2;
+      if ((int) t.host[2 * (size_t) mid + 1] < y)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    return lo;
+  };
+  q->list_lo = first_at (y0);
+  q->list_hi = first_at (y1);
+  q->width = f.width;
+  q->height = f.height;
+  q->src_stride = q->dst_stride = f.src_stride;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
+  q->hot = t.par.hot;
+  q->cold = t.par.cold;
+  q->y0 = y0;
+  q->y1 = y1;
+}
+
+extern "C" int mibayer_dpc_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream)
+{
+  if (!c || c->inverse || !d_src || !d_dst || nframes < 0 || d_dst == d_src)
+    return MIBAYER_ERR_ARG;
+  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3) || dst_frame_bytes < c->src_bytes
+          || (dst_frame_bytes & 3)))
+    return MIBAYER_ERR_GEOMETRY;
+  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_dst) & 3))
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const DpcSet> t;
+  {
+    std::lock_guard<std::mutex> lk (c->stats_mu);
+    t = c->dpc;
+  }
+  if (!t)
+    return MIBAYER_ERR_EMPTY;
+  if (nframes == 0)
+    return MIBAYER_OK;
+  DeviceGuard guard (c->device);
+  if (!guard.ok)
+    return MIBAYER_ERR_HIP;
+  Range r ("mibayer:dpc_device");
+  mark_dirty (c, (hipStream_t) hip_stream);
+  DpcParams q;
+  dpc_params (c, *t, 0, c->cfg.height, &q);
+  q.src = (const uint8_t *) d_src;
+  q.dst = (uint8_t *) d_dst;
+  q.src_frame_bytes = src_frame_bytes;
+  q.dst_frame_bytes = dst_frame_bytes;
+  HIP_TRY (launch_dpc (q, nframes, (hipStream_t) hip_stream));
+  return MIBAYER_OK;
+}
+
+/* rows [y0, y1) of the frame in slot `s`, from the mosaic its upload landed in into the one everything else reads, on
+ * the compute queue: behind the upload of rows up to y1 + 2 and before the shading pass of the same rows */
+static int slot_launch_dpc (mibayer_ctx *c, Slot &s, int y0, int y1)
+{
+  if (!s.dpc || y1 <= y0)
+    return MIBAYER_OK;
+  Range r ("mibayer:dpc");
+  DpcParams q;
+  dpc_params (c, *s.dpc, y0, y1, &q);
+  q.src = s.d_raw;
+  q.dst = s.d_src;
+  q.src_frame_bytes = q.dst_frame_bytes = c->src_bytes;
+  HIP_TRY (launch_dpc (q, 1, c->s_compute));
+  return MIBAYER_OK;
+}
+
 /* ---- host-memory frame path -------------------------------------------------------- */
 
 /* device-side frames and events of one slot; `bands`: per-band events too */
@@ -2769,6 +2953,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
   const int nb = c->host_bands;
   const int per = (tiles_y + nb - 1) / nb;
   int uploaded = 0;             /* source rows already queued for upload */
+  int final_rows = 0;           /* source rows that have had every pass over the mosaic */
   /* the band count follows the plan (choose_host_bands after every plan change) and may have grown since the slot was
    * made: the events a band needs are made when it first needs them (free_slot destroys all kMaxHostBands) */
   for (int b = 0; b < nb; b++) {
@@ -2782,18 +2967,25 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     const int t1 = t0 + per < tiles_y ? t0 + per : tiles_y;
     const int y0 = t0 * th;
     const int y1 = t1 * th < f.height ? t1 * th : f.height;
-    const int up_to = y1 + halo < f.height ? y1 + halo : f.height;     /* + the halo row below */
-    const int shade_from = uploaded;    /* the rows this band's upload brings: shaded once, before anything reads them */
+    /* + the halo row below, and while the frame is corrected the two rows under it that the correction looks at */
+    const int ahead = s.dpc ? halo + 2 : halo;
+    const int up_to = y1 + ahead < f.height ? y1 + ahead : f.height;
+    /* the rows this band's upload completes: corrected and shaded once, before anything reads them */
+    const int shade_from = s.dpc ? final_rows : uploaded;
+    final_rows = !s.dpc || up_to == f.height ? up_to : up_to - 2;
     if (up_to > uploaded) {
       const size_t off = (size_t) uploaded * f.src_stride;
-      HIP_TRY (hipMemcpyAsync (s.d_src + off, src + off,
+      HIP_TRY (hipMemcpyAsync ((s.dpc ? s.d_raw : s.d_src) + off, src + off,
               (size_t) (up_to - uploaded) * f.src_stride, hipMemcpyHostToDevice,
               c->s_h2d));
       uploaded = up_to;
     }
     HIP_TRY (hipEventRecord (s.ev_band_in[b], c->s_h2d));
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_band_in[b], 0));
-    int rc = slot_launch_shade (c, s, shade_from, up_to);
+    int rc = slot_launch_dpc (c, s, shade_from, final_rows);
+    if (rc != MIBAYER_OK)
+      return rc;
+    rc = slot_launch_shade (c, s, shade_from, final_rows);
     if (rc != MIBAYER_OK)
       return rc;
     rc = launch_frames (c, slot_frame (c, s), c->s_compute, t0, t1 - t0, c->colour ? &s.stage : nullptr);
@@ -2879,7 +3071,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 {
   {
     Range r ("mibayer:h2d");
-    HIP_TRY (hipMemcpyAsync (s.d_src, src, c->src_bytes, hipMemcpyHostToDevice,
+    HIP_TRY (hipMemcpyAsync (s.dpc ? s.d_raw : s.d_src, src, c->src_bytes, hipMemcpyHostToDevice,
             c->s_h2d));
     HIP_TRY (hipEventRecord (s.ev_in, c->s_h2d));
   }
@@ -2891,6 +3083,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
   } else {
     Range r ("mibayer:kernel");
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_in, 0));
+    const int dpc_rc = slot_launch_dpc (c, s, 0, c->cfg.height);
+    if (dpc_rc != MIBAYER_OK)
+      return dpc_rc;
     const int shade_rc = slot_launch_shade (c, s, 0, c->cfg.height);
     if (shade_rc != MIBAYER_OK)
       return shade_rc;
@@ -2936,9 +3131,10 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   if (rc != MIBAYER_OK)
     return rc;
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
-  /* (the captured graphs hold the demosaic launch only: a frame with statistics or shading is launched without them) */
+  /* (the captured graphs hold the demosaic launch only: a frame with statistics, shading or defective pixel
+   * correction is launched without them) */
   const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on
-      && !s.shade;
+      && !s.shade && !s.dpc;
   /* bands pay when this frame has the link to itself (measured at 4K: +7 %
    * synchronous, -6 % with three frames in flight, which overlap anyway) */
   if (want_graph && c->graph_mode == 1

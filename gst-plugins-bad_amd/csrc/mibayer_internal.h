@@ -384,6 +384,33 @@ struct ShadeParams {
 /* one launch over rows [p.y0, p.y1) of `nframes` frames */
 hipError_t launch_shade (const ShadeParams &p, int nframes, hipStream_t stream);
 
+/* Defective pixel correction (mosaic_dpc_kernel, mosaic_dpc_list_kernel; include/mibayer.h, group `dpc`): a 5 x 5
+ * same-site neighbourhood pass from one mosaic into a second one of the same sample format, never in place */
+constexpr int kDpcMaxRows = 64;         /* rows a workgroup walks at most */
+constexpr int kDpcMinRows = 16;         /* ... and at least, when the launch is too small to fill the device otherwise */
+constexpr int kDpcSpread = 1024;        /* workgroups a launch is spread over before the rows per workgroup grow */
+struct DpcParams {
+  const uint8_t *src;
+  uint8_t *dst;                 /* never src */
+  unsigned long long src_frame_bytes, dst_frame_bytes;
+  const uint32_t *list;         /* device memory: (x, y) pairs sorted by (y, x); the entries [list_lo, list_hi) lie in
+                                 * rows [y0, y1) (the caller bisects) */
+  int list_lo, list_hi;
+  int width, height, src_stride, dst_stride;
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a dword: identity or a byte swap per 16-bit word (its own inverse) */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  int hot, cold;                /* thresholds, -1 = off */
+  int y0, y1;                   /* rows [y0, y1) */
+  /* filled by launch_dpc */
+  int row_dwords;               /* dwords of a row that hold columns < width (the last one may hold two columns past it) */
+  int seg_rows;                 /* rows a workgroup walks */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row */
+};
+/* rows [p.y0, p.y1) of `nframes` frames: the detection and copy pass, then -- behind it on the same stream -- the
+ * listed defects of those rows */
+hipError_t launch_dpc (const DpcParams &p, int nframes, hipStream_t stream);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

@@ -2661,6 +2661,219 @@ hipError_t launch_shade (const ShadeParams &p, int nframes, hipStream_t stream)
 }
 
 /* ------------------------------------------------------------------------- */
+/* defective pixel correction                                                  */
+/* ------------------------------------------------------------------------- */
+/* out = R where S > hi + hot or S + cold < lo, else S, over the eight same-site neighbours at +-2 (include/mibayer.h,
+ * group `dpc`).  All of it is done on dwords that hold two samples in their 16-bit halves: the two words of a deep
+ * mosaic, or the even and the odd bytes of an 8-bit dword, so one body serves both widths and the 8-bit kernel calls it
+ * twice.  No value leaves its half: every sample is at most 0xffff, the differences saturate, and
+ * R = (a + b + 1) >> 1 = (a | b) - ((a ^ b) >> 1) borrows nothing. */
+typedef unsigned short dpc_u16x2 __attribute__ ((ext_vector_type (2)));
+#define DPC_V(x) __builtin_bit_cast (dpc_u16x2, (uint32_t) (x))
+#define DPC_U(v) __builtin_bit_cast (uint32_t, (v))
+__device__ __forceinline__ uint32_t dpc_max (uint32_t a, uint32_t b) { return DPC_U (__builtin_elementwise_max (DPC_V (a), DPC_V (b))); }
+__device__ __forceinline__ uint32_t dpc_min (uint32_t a, uint32_t b) { return DPC_U (__builtin_elementwise_min (DPC_V (a), DPC_V (b))); }
+/* max (a - b, 0) per half */
+__device__ __forceinline__ uint32_t dpc_over (uint32_t a, uint32_t b) { return DPC_U (__builtin_elementwise_sub_sat (DPC_V (a), DPC_V (b))); }
+/* 0xffff in the halves that are not zero: 0 - min (a, 1), two packed instructions.  `one` is 1 in both halves from a
+ * register the compiler cannot see into (mosaic_dpc_kernel): knowing the constant it turns the minimum into a compare and
+ * a select per half and puts the halves together again, seven instructions */
+__device__ __forceinline__ uint32_t dpc_any (uint32_t a, uint32_t one)
+{
+  return DPC_U (DPC_V (0u) - DPC_V (dpc_min (a, one)));
+}
+
+/* the pair (a, b) replaces the best pair so far where its gradient is smaller; the first of equals stays */
+__device__ __forceinline__ void dpc_pair (uint32_t a, uint32_t b, uint32_t &bg, uint32_t &ba, uint32_t &bb, uint32_t one)
+{
+  const uint32_t g = dpc_max (a, b) - dpc_min (a, b);
+  const uint32_t m = dpc_any (dpc_over (bg, g), one);
+  bg = dpc_min (bg, g);
+  ba = (a & m) | (ba & ~m);
+  bb = (b & m) | (bb & ~m);
+}
+
+/* rows up / mid / down of the window as (left, centre, right): the samples two columns left of, at and two columns right
+ * of the lane's; hot, cold: the thresholds in both halves, 0xffff = never */
+__device__ __forceinline__ uint32_t dpc_samples (const uint32_t *u, const uint32_t *m, const uint32_t *d, uint32_t hot, uint32_t cold,
+    uint32_t one)
+{
+  const uint32_t s = m[1];
+  const uint32_t hi = dpc_max (dpc_max (dpc_max (u[0], u[1]), dpc_max (u[2], m[0])),
+      dpc_max (dpc_max (m[2], d[0]), dpc_max (d[1], d[2])));
+  const uint32_t lo = dpc_min (dpc_min (dpc_min (u[0], u[1]), dpc_min (u[2], m[0])),
+      dpc_min (dpc_min (m[2], d[0]), dpc_min (d[1], d[2])));
+  const uint32_t bad = dpc_any (dpc_over (dpc_over (s, hi), hot) | dpc_over (dpc_over (lo, s), cold), one);
+  uint32_t ba = m[0], bb = m[2];                                                /* H */
+  uint32_t bg = dpc_max (ba, bb) - dpc_min (ba, bb);
+  dpc_pair (u[1], d[1], bg, ba, bb, one);                                            /* V */
+  dpc_pair (u[0], d[2], bg, ba, bb, one);                                            /* D1 */
+  dpc_pair (u[2], d[0], bg, ba, bb, one);                                            /* D2 */
+  const uint32_t r = (ba | bb) - (((ba ^ bb) >> 1) & 0x7fff7fffu);
+  return (r & bad) | (s & ~bad);
+}
+
+/* The detection and copy pass.  A workgroup is four waves side by side, each on a strip of 64 dwords, walking seg_rows
+ * rows; a lane owns a dword column and holds a rolling window of five rows plus the one in flight, each as the dwords
+ * left of, at and right of its own (three coalesced loads per row; the neighbours' come from the cache), so a row is
+ * fetched once per segment plus four halo rows.  The row three below is requested before the current row is computed and
+ * unpacked after it: a load has a whole row of arithmetic to arrive in.  The borders are substituted at load time: the
+ * row index is mirrored around the pixel (t - 2 < 0 -> t + 2 is row t + 4 of the loaded one) and the dword off the row's
+ * end is replaced by the one on the other side.  Of an 8-bit mosaic the samples two columns away are the two halves of a
+ * byte-aligned pair of dwords, and a row is kept as its even and its odd bytes (NP = 2 dwords of packed halves per
+ * position); a row whose width is 2 mod 4 ends in half a dword, which takes its right-hand neighbours from its upper
+ * half and is stored as 16 bits. */
+template <bool IN8>
+__global__ void __launch_bounds__ (256)
+mosaic_dpc_kernel (DpcParams p)
+{
+  constexpr int NP = IN8 ? 2 : 1;
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int ya = p.y0 + (int) blockIdx.y * p.seg_rows;          /* < y1 (launch_dpc) */
+  const int yb = ya + p.seg_rows < p.y1 ? ya + p.seg_rows : p.y1;
+  const int g = (int) (strip * 256u + threadIdx.x);             /* dword of the row */
+  if (g >= p.row_dwords)
+    return;
+  const int last = p.row_dwords - 1;
+  const bool tail = IN8 && 4 * g + 2 >= p.width;                /* columns 4 g + 2, 4 g + 3 are past the row's end */
+  const int gl = g > 0 ? g - 1 : IN8 ? g : g + 1;               /* 0 .. last, as is gr */
+  const int gr = g < last ? g + 1 : IN8 ? g : g - 1;
+  const uint32_t hot = p.hot < 0 ? 0xffffffffu : (uint32_t) p.hot * 0x10001u;
+  const uint32_t cold = p.cold < 0 ? 0xffffffffu : (uint32_t) p.cold * 0x10001u;
+  uint32_t one = 0x00010001u;
+  asm ("" : "+v" (one));        /* dpc_any */
+  const uint8_t *sbase = p.src + frame * p.src_frame_bytes;
+  uint8_t *dcol = p.dst + frame * p.dst_frame_bytes + 4 * (size_t) g;
+  /* row t of the window, -2 <= t < height + 2: rows 0 .. height - 1 of the source only (height >= 4); past the
+   * segment's own halo nothing is needed, and the last row asked for is loaded again */
+  auto load_row = [&] (int t, uint32_t (&raw)[3]) {
+    t = t < yb + 1 ? t : yb + 1;
+    const int r = t < 0 ? t + 4 : t >= p.height ? t - 4 : t;
+    const uint32_t *row = (const uint32_t *) (sbase + (size_t) r * (size_t) p.src_stride);
+    raw[0] = row[gl];
+    raw[1] = row[g];
+    raw[2] = row[gr];
+  };
+  /* the loaded dwords as (left, centre, right) of packed halves: w[j * NP + k] */
+  auto unpack_row = [&] (const uint32_t (&raw)[3], uint32_t (&w)[3 * NP]) {
+    if (IN8) {
+      const uint32_t b = tail ? (raw[1] & 0xffffu) | (raw[0] & 0xffff0000u) : raw[1];
+      const uint32_t t[3] = { __builtin_amdgcn_alignbyte (b, raw[0], 2), b, __builtin_amdgcn_alignbyte (raw[2], b, 2) };
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        w[j * NP] = t[j] & 0x00ff00ffu;
+        w[j * NP + NP - 1] = (t[j] >> 8) & 0x00ff00ffu;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+        w[j * NP] = __builtin_amdgcn_perm (raw[j], raw[j], p.in_sel) & p.mask2;
+    }
+  };
+  uint32_t w[5][3 * NP], raw[3];
+#pragma unroll
+  for (int k = 0; k < 5; k++) {
+    load_row (ya - 2 + k, raw);
+    unpack_row (raw, w[k]);
+  }
+  for (int y = ya; y < yb; y++) {       /* uniform over the workgroup */
+    load_row (y + 3, raw);
+    uint32_t o;
+    if (IN8) {
+      const uint32_t ue[3] = { w[0][0], w[0][2], w[0][4] }, me[3] = { w[2][0], w[2][2], w[2][4] }, de[3] = { w[4][0], w[4][2], w[4][4] };
+      const uint32_t uo[3] = { w[0][1], w[0][3], w[0][5] }, mo[3] = { w[2][1], w[2][3], w[2][5] }, dq[3] = { w[4][1], w[4][3], w[4][5] };
+      o = dpc_samples (ue, me, de, hot, cold, one) | (dpc_samples (uo, mo, dq, hot, cold, one) << 8);
+    } else {
+      o = dpc_samples (w[0], w[2], w[4], hot, cold, one);
+      o = __builtin_amdgcn_perm (o, o, p.in_sel);
+    }
+    uint8_t *out = dcol + (size_t) y * (size_t) p.dst_stride;
+    if (tail)
+      *(uint16_t *) out = (uint16_t) o;
+    else
+      __builtin_nontemporal_store (o, (uint32_t *) out);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+      for (int j = 0; j < 3 * NP; j++)
+        w[k][j] = w[k + 1][j];
+    unpack_row (raw, w[4]);
+  }
+}
+
+/* The listed defects of rows [y0, y1): one lane per entry [list_lo, list_hi) and frame, behind the pass above on the
+ * same stream.  R is computed from the source, so an entry the detection has flagged too receives the same value. */
+__global__ void __launch_bounds__ (256)
+mosaic_dpc_list_kernel (DpcParams p)
+{
+  const uint32_t per = ((uint32_t) (p.list_hi - p.list_lo) + 255u) / 256u;     /* workgroups per frame */
+  const uint32_t frame = blockIdx.x / per;
+  const int e = p.list_lo + (int) ((blockIdx.x - frame * per) * 256u + threadIdx.x);
+  if (e >= p.list_hi)
+    return;
+  const int x = (int) p.list[2 * e], y = (int) p.list[2 * e + 1];       /* inside the frame (mibayer_set_dpc) */
+  const int xl = x >= 2 ? x - 2 : x + 2, xr = x + 2 < p.width ? x + 2 : x - 2;
+  const int yu = y >= 2 ? y - 2 : y + 2, yd = y + 2 < p.height ? y + 2 : y - 2;
+  const uint8_t *src = p.src + frame * p.src_frame_bytes;
+  auto at = [&] (int xx, int yy) -> int {
+    const uint8_t *row = src + (size_t) yy * (size_t) p.src_stride;
+    if (p.in8)
+      return row[xx];
+    const uint32_t v = ((const uint16_t *) row)[xx];
+    return (int) (__builtin_amdgcn_perm (v, v, p.in_sel) & p.mask2 & 0xffffu);
+  };
+  const int pa[4] = { at (xl, y), at (x, yu), at (xl, yu), at (xr, yu) };
+  const int pb[4] = { at (xr, y), at (x, yd), at (xr, yd), at (xl, yd) };
+  int bg = 0x10000, r = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int gk = pa[k] > pb[k] ? pa[k] - pb[k] : pb[k] - pa[k];
+    if (gk < bg) {
+      bg = gk;
+      r = (pa[k] + pb[k] + 1) >> 1;
+    }
+  }
+  uint8_t *out = p.dst + frame * p.dst_frame_bytes + (size_t) y * (size_t) p.dst_stride;
+  if (p.in8)
+    out[x] = (uint8_t) r;
+  else
+    ((uint16_t *) out)[x] = (uint16_t) __builtin_amdgcn_perm ((uint32_t) r, (uint32_t) r, p.in_sel);
+}
+
+hipError_t launch_dpc (const DpcParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.width < 4 || (p.width & 1) || p.height < 4 || p.y0 < 0 || p.y1 <= p.y0 || p.y1 > p.height || p.dst == p.src
+      || p.list_lo < 0 || p.list_hi < p.list_lo || (p.list_hi > p.list_lo && !p.list))
+    return hipErrorInvalidValue;        /* (a mirrored row or dword outside the frame) */
+  DpcParams q = p;
+  q.row_dwords = p.in8 ? (p.width + 3) / 4 : p.width / 2;
+  const long long strips = (q.row_dwords + 255) / 256;
+  /* rows per workgroup as in launch_shade: as many as kDpcMaxRows, cut finer until the launch has kDpcSpread workgroups */
+  const long long h = p.y1 - p.y0;
+  long long rows = h * strips * nframes / kDpcSpread;
+  rows = rows < kDpcMinRows ? kDpcMinRows : rows > kDpcMaxRows ? kDpcMaxRows : rows;
+  if ((h + rows - 1) / rows > 65535)
+    rows = (h + 65534) / 65535;
+  const long long gy = (h + rows - 1) / rows;
+  const long long per = ((long long) (p.list_hi - p.list_lo) + 255) / 256;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535 || per * nframes > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  q.seg_rows = (int) rows;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  const dim3 grid ((unsigned) (strips * nframes), (unsigned) gy);
+  if (p.in8)
+    hipLaunchKernelGGL (mosaic_dpc_kernel<true>, grid, dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL (mosaic_dpc_kernel<false>, grid, dim3 (256), 0, stream, q);
+  if (per > 0)
+    hipLaunchKernelGGL (mosaic_dpc_list_kernel, dim3 ((unsigned) (per * nframes)), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

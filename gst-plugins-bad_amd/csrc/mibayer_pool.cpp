@@ -64,6 +64,8 @@
 #pragma weak mibayer_frame_hist
 /* ... and the shading table's: mibayer_pool_set_shading is refused there too */
 #pragma weak mibayer_set_shading
+/* ... and the defective pixel correction's: mibayer_pool_set_dpc is refused there too */
+#pragma weak mibayer_set_dpc
 
 #include <sched.h>
 
@@ -92,6 +94,11 @@ struct StatsGrid {
 struct ShadeSet {
   mibayer_shading par;
   std::vector<uint16_t> table;
+};
+/* what mibayer_pool_set_dpc asked for: the parameters and the pool's copy of the list (par.defects points into it) */
+struct DpcAsk {
+  mibayer_dpc par;
+  std::vector<uint32_t> list;
 };
 /* a frame's histogram rides behind its zones in the same vector, as it does in a context's slot */
 constexpr size_t kHistZones = sizeof (mibayer_hist) / sizeof (mibayer_stats_zone);
@@ -126,6 +133,7 @@ struct Frame {
   std::vector<mibayer_stats_zone> zones;
   /* mibayer_pool_set_shading: the table the pool held when the frame was accepted (NULL: none), applied like the stage */
   std::shared_ptr<const ShadeSet> shade;
+  std::shared_ptr<const DpcAsk> dpc;            /* mibayer_pool_set_dpc: likewise */
 };
 
 struct Shard {
@@ -141,6 +149,7 @@ struct Shard {
                                                            thread hands frames to the context) */
   std::shared_ptr<const StatsGrid> applied_grid;        /* ... and the statistics grid (NULL: off, as created) */
   std::shared_ptr<const ShadeSet> applied_shade;        /* ... and the shading table (NULL: off, as created) */
+  std::shared_ptr<const DpcAsk> applied_dpc;            /* ... and the defective pixel correction (likewise) */
   std::atomic<long long> completions { 0 };
   std::atomic<long long> fail_after { -1 };     /* fault injection; -1 = never */
   /* helper thread */
@@ -190,10 +199,20 @@ void apply_shading (Shard *sh, const Frame *f)
     sh->applied_shade = f->shade;
 }
 
+/* the same for the frame's defective pixel correction */
+void apply_dpc (Shard *sh, const Frame *f)
+{
+  if (f->dpc == sh->applied_dpc || !mibayer_set_dpc)
+    return;
+  if (mibayer_set_dpc (sh->ctx, f->dpc ? &f->dpc->par : NULL) == MIBAYER_OK)
+    sh->applied_dpc = f->dpc;
+}
+
 /* the same for the frame's statistics grid (and, with it, the shading table: the two travel together) */
 void apply_stats (Shard *sh, const Frame *f)
 {
   apply_shading (sh, f);
+  apply_dpc (sh, f);
   if (f->grid == sh->applied_grid || !mibayer_set_stats)
     return;
   const StatsGrid off = {};
@@ -403,6 +422,7 @@ struct mibayer_pool {
   bool has_zones = false;
   std::shared_ptr<const StatsGrid> last_grid;   /* ... which says what last_zones holds */
   std::shared_ptr<const ShadeSet> shade;        /* mibayer_pool_set_shading: the table of the frames submitted from now on */
+  std::shared_ptr<const DpcAsk> dpc;            /* mibayer_pool_set_dpc: likewise */
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -868,6 +888,38 @@ extern "C" int mibayer_pool_set_shading (mibayer_pool *pool, const mibayer_shadi
   return MIBAYER_OK;
 }
 
+/* The defective pixel correction of the frames submitted from now on, kept with each frame like the shading table
+ * (apply_dpc); the rules are the context layer's (include/mibayer.h), restated on the resolved configuration. */
+extern "C" int mibayer_pool_set_dpc (mibayer_pool *pool, const mibayer_dpc *dpc)
+{
+  if (!pool || !mibayer_set_dpc)
+    return MIBAYER_ERR_ARG;
+  if (!dpc) {
+    pool->dpc.reset ();
+    return MIBAYER_OK;
+  }
+  mibayer_cfg f;
+  if (mibayer_get_cfg (pool->shards[0]->ctx, &f) != MIBAYER_OK || (f.flags & MIBAYER_FLAG_RGB2BAYER)
+      || dpc->struct_size != sizeof (mibayer_dpc))
+    return MIBAYER_ERR_ARG;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const int vmax = bits ? (1 << bits) - 1 : 255;
+  if (dpc->hot < -1 || dpc->hot > vmax || dpc->cold < -1 || dpc->cold > vmax || dpc->ndefects > MIBAYER_DPC_MAX_DEFECTS
+      || (dpc->ndefects > 0 && !dpc->defects))
+    return MIBAYER_ERR_ARG;
+  for (uint32_t e = 0; e < dpc->ndefects; e++)
+    if (dpc->defects[2 * e] >= (uint32_t) f.width || dpc->defects[2 * e + 1] >= (uint32_t) f.height)
+      return MIBAYER_ERR_ARG;
+  if (f.height < 4)
+    return MIBAYER_ERR_GEOMETRY;
+  auto set = std::make_shared<DpcAsk> ();
+  set->list.assign (dpc->defects, dpc->defects + 2 * (size_t) dpc->ndefects);
+  set->par = *dpc;
+  set->par.defects = set->list.data ();
+  pool->dpc = set;
+  return MIBAYER_OK;
+}
+
 extern "C" int mibayer_pool_inject_stall (mibayer_pool *pool, int shard, int ms)
 {
   if (!pool || shard < 0 || shard >= (int) pool->shards.size ())
@@ -955,7 +1007,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       sh->stall_ms = 0;
       (void) mibayer_internal_stall (sh->ctx, ms);
     }
-    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {}, pool->shade };
+    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {}, pool->shade, pool->dpc };
     if (pool->use_helpers && (mibayer_internal_is_pageable (src) || mibayer_internal_is_pageable (dst))
         && !sh->pageable_seen) {
       sh->pageable_seen = true;

@@ -82,12 +82,17 @@ enum
   PROP_METHOD,
   PROP_COLOUR_FIRST,            /* GST_MI_COLOUR_N_PROPS ids (gstmicolour.h) */
   PROP_COLOUR_LAST = PROP_COLOUR_FIRST + GST_MI_COLOUR_N_PROPS - 1,
-  PROP_SHADING_FILE
+  PROP_SHADING_FILE,
+  PROP_DPC_HOT,
+  PROP_DPC_COLD,
+  PROP_DEFECT_FILE
 };
 
 /* bound weakly, like the colour stage's entry points (gstmicolour.h): over a libmibayer without lens shading
  * correction a shading-file is an element error */
 #pragma weak mibayer_pool_set_shading
+/* ... and over one without defective pixel correction a threshold or a defect-file is */
+#pragma weak mibayer_pool_set_dpc
 
 #define DEFAULT_DEVICE_ID 0
 #define DEFAULT_INFLIGHT 1
@@ -510,6 +515,83 @@ done:
   return why;
 }
 
+/* dpc-hot-threshold, dpc-cold-threshold, defect-file: reads the list (text, one `x y` per line, `#` starts a comment,
+ * blank lines allowed), checks it against the negotiated size and hands it with the thresholds to the pool; NULL, or
+ * why not (a string the caller owns) */
+static gchar *
+element_load_dpc (GstMiBayerElement * self)
+{
+  gchar *data = NULL, *why = NULL;
+  GError *err = NULL;
+  GArray *xy = g_array_new (FALSE, FALSE, sizeof (guint32));
+  mibayer_dpc dpc;
+  int rc;
+
+  if (!mibayer_pool_set_dpc) {
+    why = g_strdup ("this libmibayer has no defective pixel correction");
+    goto done;
+  }
+  if (self->act.defect_file && self->act.defect_file[0]) {
+    gchar **lines, **l;
+
+    if (!g_file_get_contents (self->act.defect_file, &data, NULL, &err)) {
+      why = g_strdup (err->message);
+      g_clear_error (&err);
+      goto done;
+    }
+    lines = g_strsplit (data, "\n", -1);
+    for (l = lines; *l && !why; l++) {
+      gchar *hash = strchr (*l, '#'), *end;
+      guint64 v[2];
+      const gchar *s;
+      int k;
+
+      if (hash)
+        *hash = 0;
+      s = g_strstrip (*l);
+      if (!*s)
+        continue;
+      for (k = 0; k < 2; k++) {
+        if (!g_ascii_isdigit (*s))
+          break;
+        v[k] = g_ascii_strtoull (s, &end, 10);
+        s = end;
+        while (*s == ' ' || *s == '\t')
+          s++;
+      }
+      if (k < 2 || *s)
+        why = g_strdup_printf ("line %d is not `x y`", (int) (l - lines) + 1);
+      else if (v[0] >= (guint64) self->width || v[1] >= (guint64) self->height)
+        why = g_strdup_printf ("line %d: (%" G_GUINT64_FORMAT ", %" G_GUINT64_FORMAT ") lies outside a %dx%d frame",
+            (int) (l - lines) + 1, v[0], v[1], self->width, self->height);
+      else if (xy->len >= 2 * MIBAYER_DPC_MAX_DEFECTS)
+        why = g_strdup_printf ("more than %d defects", MIBAYER_DPC_MAX_DEFECTS);
+      else {
+        guint32 x = (guint32) v[0], y = (guint32) v[1];
+
+        g_array_append_val (xy, x);
+        g_array_append_val (xy, y);
+      }
+    }
+    g_strfreev (lines);
+    if (why)
+      goto done;
+  }
+  memset (&dpc, 0, sizeof dpc);
+  dpc.struct_size = sizeof dpc;
+  dpc.hot = self->act.dpc_hot;
+  dpc.cold = self->act.dpc_cold;
+  dpc.ndefects = xy->len / 2;
+  dpc.defects = xy->len ? (const guint32 *) xy->data : NULL;
+  rc = mibayer_pool_set_dpc (self->pool, &dpc);
+  if (rc != MIBAYER_OK)
+    why = g_strdup_printf ("mibayer_pool_set_dpc: %s", mibayer_strerror (rc));
+done:
+  g_array_free (xy, TRUE);
+  g_free (data);
+  return why;
+}
+
 /* `video_stride` is the mapped stride of the 4-byte-per-pixel frame (8 bytes
  * for ARGB64): the destination stride of bayer2rgb (reference
  * gstbayer2rgb.c:476), the source stride of rgb2bayer (gstrgb2bayer.c:256).
@@ -640,6 +722,19 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       return FALSE;
     }
   }
+  if (!inverse && (self->act.dpc_hot >= 0 || self->act.dpc_cold >= 0 || (self->act.defect_file && self->act.defect_file[0]))) {
+    gchar *why = element_load_dpc (self);
+
+    if (why) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up defective pixel correction (dpc-hot-threshold=%d dpc-cold-threshold=%d "
+              "defect-file=\"%s\")", LABEL (self), self->act.dpc_hot, self->act.dpc_cold,
+              self->act.defect_file ? self->act.defect_file : ""), why);
+      return FALSE;
+    }
+  }
   if (want_colour && ((GstMiColourProps *) self->act.colour)->white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD) {
     guint32 lo, hi;
 
@@ -730,6 +825,16 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
       g_free (self->shading_file);
       self->shading_file = g_value_dup_string (value);
       break;
+    case PROP_DPC_HOT:
+      self->dpc_hot = g_value_get_int (value);
+      break;
+    case PROP_DPC_COLD:
+      self->dpc_cold = g_value_get_int (value);
+      break;
+    case PROP_DEFECT_FILE:
+      g_free (self->defect_file);
+      self->defect_file = g_value_dup_string (value);
+      break;
     default:
       if (gst_mi_colour_set_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -771,6 +876,15 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
     case PROP_SHADING_FILE:
       g_value_set_string (value, self->shading_file ? self->shading_file : "");
       break;
+    case PROP_DPC_HOT:
+      g_value_set_int (value, self->dpc_hot);
+      break;
+    case PROP_DPC_COLD:
+      g_value_set_int (value, self->dpc_cold);
+      break;
+    case PROP_DEFECT_FILE:
+      g_value_set_string (value, self->defect_file ? self->defect_file : "");
+      break;
     default:
       if (gst_mi_colour_get_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -795,6 +909,9 @@ element_finalize (GObject * object)
   g_free (self->shading_file);
   g_free (self->act.shading_file);
   self->shading_file = self->act.shading_file = NULL;
+  g_free (self->defect_file);
+  g_free (self->act.defect_file);
+  self->defect_file = self->act.defect_file = NULL;
   if (self->colour) {
     gst_mi_colour_props_clear (self->colour);
     gst_mi_colour_props_clear (self->act.colour);
@@ -1354,6 +1471,10 @@ element_start (GstBaseTransform * base)
   self->act.method = self->method;
   g_free (self->act.shading_file);
   self->act.shading_file = g_strdup (self->shading_file);
+  self->act.dpc_hot = self->dpc_hot;
+  self->act.dpc_cold = self->dpc_cold;
+  g_free (self->act.defect_file);
+  self->act.defect_file = g_strdup (self->defect_file);
   gst_mi_colour_props_copy (self->act.colour, self->colour);
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
@@ -1449,6 +1570,30 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             "writes one); must fit the negotiated size; empty = off", "",
             G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
             G_PARAM_STATIC_STRINGS));
+  if (!inverse) {
+    g_object_class_install_property (object_class, PROP_DPC_HOT,
+        g_param_spec_int ("dpc-hot-threshold", "Hot pixel threshold",
+            "Defective pixel correction on the mosaic, before everything else: a "
+            "sample more than this above its eight same-colour neighbours (two "
+            "pixels away) is replaced from the flattest pair of them; at the "
+            "depth of the mosaic; -1 = off", -1, 65535, -1,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_DPC_COLD,
+        g_param_spec_int ("dpc-cold-threshold", "Cold pixel threshold",
+            "Likewise for a sample more than this below its eight same-colour "
+            "neighbours; -1 = off", -1, 65535, -1,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_DEFECT_FILE,
+        g_param_spec_string ("defect-file", "Known defective pixels",
+            "Text file with the known defective pixels, corrected whatever the "
+            "thresholds say: one `x y` per line, `#` starts a comment, blank "
+            "lines are allowed; read when the caps are set; every pixel must lie "
+            "inside the negotiated frame; empty = none", "",
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+  }
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
   transform_class->get_unit_size = GST_DEBUG_FUNCPTR (element_get_unit_size);
@@ -1478,6 +1623,7 @@ gst_mi_bayer_element_instance_setup (GstMiBayerElement * self)
   self->timeout_ms = DEFAULT_TIMEOUT_MS;
   self->act.timeout_ms = DEFAULT_TIMEOUT_MS;
   self->method = DEFAULT_METHOD;
+  self->dpc_hot = self->dpc_cold = self->act.dpc_hot = self->act.dpc_cold = -1;
   self->act.method = DEFAULT_METHOD;
   self->colour = g_new0 (GstMiColourProps, 1);
   self->act.colour = g_new0 (GstMiColourProps, 1);

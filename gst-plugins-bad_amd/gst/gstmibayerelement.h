@@ -62,6 +62,8 @@ struct _GstMiBayerElement
   gint method;                  /* GstMiBayerMethod (bayer2rgb only) */
   gpointer colour;              /* GstMiColourProps* (gstmicolour.h; bayer2rgb only): the colour-stage properties */
   gchar *shading_file;          /* lens shading table (bayer2rgb only); NULL or "" = off */
+  gint dpc_hot, dpc_cold;       /* defective pixel correction thresholds (bayer2rgb only); -1 = off */
+  gchar *defect_file;           /* list of known defects (bayer2rgb only); NULL or "" = none */
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -76,6 +78,8 @@ struct _GstMiBayerElement
     gint method;
     gpointer colour;            /* GstMiColourProps* */
     gchar *shading_file;
+    gint dpc_hot, dpc_cold;
+    gchar *defect_file;
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;

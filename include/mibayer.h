@@ -74,6 +74,8 @@ extern "C" {
  * point was added, and a cfg without the flag means what it meant. */
 /* 5, later additive: lens shading correction -- struct mibayer_shading and the entry points of group `shading`; a
  * context without a table converts what it converted. */
+/* 5, later additive: defective pixel correction -- struct mibayer_dpc and the entry points of group `dpc`; a context
+ * with the correction off converts what it converted. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -108,6 +110,9 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group dpc: defective pixel correction -- stuck samples of the mosaic, found by threshold against their same-site
+ *   neighbours or named in a list, replaced from the flattest neighbour pair before everything else reads them
+ *     mibayer_set_dpc mibayer_get_dpc mibayer_dpc_device mibayer_pool_set_dpc
  * group shading: lens shading correction -- a per-site gain grid applied to the mosaic before everything else reads it,
  *   and the helper that turns flat-field zone statistics into such a grid
  *     mibayer_shading_nodes mibayer_set_shading mibayer_get_shading mibayer_shade_device mibayer_pool_set_shading
@@ -541,6 +546,67 @@ int mibayer_pool_set_shading (mibayer_pool *pool, const mibayer_shading *shading
  * included). */
 int mibayer_stats_shading (const mibayer_stats_zone *zones, int zones_x, int zones_y, int width, int height,
     const uint32_t black[4], int kx, int ky, double max_gain, uint16_t *table_out);
+
+/* ---- defective pixel correction (additive within version 5: a struct and the entry points of group `dpc`) -------- */
+
+/* Stuck and dead samples, corrected on the MOSAIC before the shading pass, the statistics, the histogram and the
+ * demosaic read it.  Integers only, bit-exact.
+ *   sample   S at (x, y), depth, max = 2^depth - 1 and site exactly as in group `stats`; a deep sample is masked and
+ *            byte-swapped on read as in group `shading`
+ *   neighbours  the eight samples of the same site at (x + dx, y + dy), dx, dy in {-2, 0, 2}, not both 0.  A coordinate
+ *            off the frame is replaced by the one on the other side of the pixel: x - 2 < 0 -> x + 2, x + 2 >= W ->
+ *            x - 2, and the same for y with H.  This keeps the site and needs W >= 4 (every context) and H >= 4 (a
+ *            context with H = 3: MIBAYER_ERR_GEOMETRY).  hi = the largest, lo = the smallest of the eight
+ *   detect   hot and cold thresholds at native depth, -1 = off, else 0 .. max:
+ *              hot:  S > hi + hot            cold:  S + cold < lo
+ *   replace  four pairs, in this order:  H (x-2, y), (x+2, y)   V (x, y-2), (x, y+2)   D1 (x-2, y-2), (x+2, y+2)
+ *            D2 (x+2, y-2), (x-2, y+2).  g = |a - b| per pair; the pair with the smallest g wins, the first in that
+ *            order among equals; R = (a + b + 1) >> 1
+ *   out      R if the sample is hot, cold or listed, else S.  Neighbours are always those of the SOURCE, never
+ *            corrected values: out is a pure function of the source frame, which is why the pass cannot run in place.
+ *            Two listed defects of one site two pixels apart therefore see each other (open item: excluding listed
+ *            neighbours from the pairs).  A deep sample is written as the 16-bit word in the source's byte order with
+ *            the bits above `bits` zero.  Only the first W samples of a row are written: the stride padding of the
+ *            destination keeps what it held.
+ *   list     up to MIBAYER_DPC_MAX_DEFECTS (x, y) pairs, uint32_t xy[2 n], in any order; the library keeps a copy sorted
+ *            by (y, x) with duplicates dropped.  A coordinate outside the frame: MIBAYER_ERR_ARG.
+ * Both thresholds off and an empty list is the identity on the masked samples. */
+typedef struct mibayer_dpc {
+  uint32_t struct_size;         /* = sizeof (mibayer_dpc) */
+  int32_t hot;                  /* -1 = off, else 0 .. max */
+  int32_t cold;                 /* likewise */
+  uint32_t ndefects;            /* <= MIBAYER_DPC_MAX_DEFECTS */
+  const uint32_t *defects;      /* host memory, x0 y0 x1 y1 ...; copied; may be NULL when ndefects = 0 */
+} mibayer_dpc;
+#define MIBAYER_DPC_MAX_DEFECTS 65536
+
+/* Sets the correction of a context (NULL: off, the default).  Valid on every bayer2rgb context; MIBAYER_ERR_ARG on an
+ * RGB2BAYER context, a bad struct_size, a threshold outside -1 .. max, ndefects above the maximum, a NULL list with
+ * ndefects > 0 and a coordinate outside the frame; MIBAYER_ERR_GEOMETRY on a context with H < 4.  The list is copied
+ * into device memory of the context before the call returns.  It applies to the frames accepted (mibayer_submit /
+ * mibayer_process_host) and the mibayer_dpc_device calls made after it returns; frames already accepted keep the
+ * parameters they were accepted with.  May be called between frames, from any thread.
+ * HOST PATH: while the correction is set, a ring slot holds a second device mosaic (allocated when first needed, freed
+ * with the slot): the upload lands there and the pass writes the slot's mosaic, each row exactly once (band by band
+ * when the frame is launched in bands, two rows behind the upload), before the shading pass -- which then runs in
+ * place on corrected samples -- and before anything else reads it.  While it is set a MIBAYER_FLAG_HIPGRAPH context
+ * launches without graphs.  With the correction off nothing new is called or allocated and the bytes are those of the
+ * same context before this entry point existed.  mibayer_process_device[_list] never corrects.
+ * mibayer_get_dpc: MIBAYER_ERR_EMPTY when off; else the parameters, with out->defects pointing at the context's sorted,
+ * de-duplicated copy (valid until the next mibayer_set_dpc / mibayer_destroy) and out->ndefects its length. */
+int mibayer_set_dpc (mibayer_ctx *ctx, const mibayer_dpc *dpc);
+int mibayer_get_dpc (const mibayer_ctx *ctx, mibayer_dpc *out);
+/* Device path: one batch, `nframes` mosaics corrected with the parameters set before, frame f read at d_src + f *
+ * src_frame_bytes (rows of cfg.src_stride bytes) and written at d_dst + f * dst_frame_bytes in the same layout.  Out of
+ * place only: d_dst == d_src is MIBAYER_ERR_ARG, and any other overlap of source and destination is undefined.  The
+ * other errors are those of mibayer_shade_device; MIBAYER_ERR_EMPTY when the correction is off.  Covered by
+ * mibayer_sync when launched on the context's stream. */
+int mibayer_dpc_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream);
+/* ... of a pool: the correction of the frames mibayer_pool_submit accepts after it returns (NULL: off), kept with each
+ * frame and handed to a shard's context together with the frame, like the shading table.  Call it from the thread that
+ * calls mibayer_pool_submit. */
+int mibayer_pool_set_dpc (mibayer_pool *pool, const mibayer_dpc *dpc);
 
 /* ---- global ------------------------------------------------------------- */
 
