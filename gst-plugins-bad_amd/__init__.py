@@ -241,6 +241,34 @@ class Dpc(ctypes.Structure):
         self.defects = None if defects is None or not len(self._list) else self._list.ctypes.data
 
 
+NR_NODES = 17
+
+
+class Nr(ctypes.Structure):
+    """struct mibayer_nr (include/mibayer.h): the threshold curve of the noise reduction, 17 nodes at the levels
+    i << (depth - 4).  Nr(curve): a sequence of 17 thresholds, or one number for a constant curve."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("curve", ctypes.c_uint16 * NR_NODES), ("reserved", ctypes.c_uint16)]
+
+    def __init__(self, curve=0):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(Nr)
+        nodes = [int(curve)] * NR_NODES if np.isscalar(curve) else [int(v) for v in curve]
+        if len(nodes) != NR_NODES:
+            raise ValueError("a noise reduction curve has %d nodes" % NR_NODES)
+        self.curve[:] = nodes
+
+    def nodes(self):
+        return list(self.curve)
+
+
+def nr_curve(bits, black=0.0, read_noise=2.0, shot_noise=0.0, strength=1.0):
+    """mibayer_nr_curve: the Nr of a sensor's noise model at depth `bits`"""
+    out = Nr()
+    _check(lib().mibayer_nr_curve(int(bits), float(black), float(read_noise), float(shot_noise), float(strength),
+                                  ctypes.byref(out)), "mibayer_nr_curve")
+    return out
+
+
 HIST_BINS = 256
 
 
@@ -429,6 +457,12 @@ ABI = {
     "mibayer_get_dpc": (ctypes.c_int, [_vp, ctypes.POINTER(Dpc)]),
     "mibayer_dpc_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
     "mibayer_pool_set_dpc": (ctypes.c_int, [_vp, ctypes.POINTER(Dpc)]),
+    "mibayer_set_nr": (ctypes.c_int, [_vp, ctypes.POINTER(Nr)]),
+    "mibayer_get_nr": (ctypes.c_int, [_vp, ctypes.POINTER(Nr)]),
+    "mibayer_nr_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.c_int, _vp]),
+    "mibayer_pool_set_nr": (ctypes.c_int, [_vp, ctypes.POINTER(Nr)]),
+    "mibayer_nr_curve": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.POINTER(Nr)]),
     "mibayer_stats_shading": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.c_int,
                                              ctypes.c_double, _vp]),
@@ -593,6 +627,10 @@ class Pool:
         now on"""
         _check(lib().mibayer_pool_set_dpc(self._h, None if dpc is None else ctypes.byref(dpc)), "mibayer_pool_set_dpc")
 
+    def set_nr(self, nr):
+        """mibayer_pool_set_nr: the noise reduction curve (an Nr, or None = off) of the frames submitted from now on"""
+        _check(lib().mibayer_pool_set_nr(self._h, None if nr is None else ctypes.byref(nr)), "mibayer_pool_set_nr")
+
     def submit(self, src, dst, tag=0):
         _check(lib().mibayer_pool_submit(self._h, _ptr(src), _ptr(dst), _vp(tag)), "mibayer_pool_submit")
 
@@ -753,6 +791,28 @@ class Context:
         pitch = src_frame_bytes or self.src_bytes
         _check(lib().mibayer_dpc_device(self._h, _vp(d_src), pitch, _vp(d_dst), (dst_frame_bytes or pitch), nframes,
                                         _vp(s)), "mibayer_dpc_device")
+
+    # -- noise reduction ----------------------------------------------------------------------
+    def set_nr(self, nr):
+        """mibayer_set_nr: the curve (an Nr, or None = off) of the host-path frames accepted and the nr_device calls
+        made from now on"""
+        _check(lib().mibayer_set_nr(self._h, None if nr is None else ctypes.byref(nr)), "mibayer_set_nr")
+
+    def get_nr(self):
+        """mibayer_get_nr: None when off, else the 17 nodes"""
+        out = Nr()
+        rc = lib().mibayer_get_nr(self._h, ctypes.byref(out))
+        if rc == ERR_EMPTY:
+            return None
+        _check(rc, "mibayer_get_nr")
+        return out.nodes()
+
+    def nr_device(self, d_src, d_dst, nframes=1, src_frame_bytes=None, dst_frame_bytes=None, stream="ctx"):
+        """mibayer_nr_device: nframes mosaics at d_src denoised into d_dst (never d_src) with the curve set"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        pitch = src_frame_bytes or self.src_bytes
+        _check(lib().mibayer_nr_device(self._h, _vp(d_src), pitch, _vp(d_dst), (dst_frame_bytes or pitch), nframes,
+                                       _vp(s)), "mibayer_nr_device")
 
     # -- mosaic zone statistics -------------------------------------------------------------
     def stats_device(self, d_src, d_stats, zones_x, zones_y, lo, hi, nframes=1, src_frame_bytes=None, stream="ctx"):

@@ -209,6 +209,10 @@ struct Slot {
    * when the slot first needs one, and the pass writes d_src */
   std::shared_ptr<const DpcSet> dpc;
   uint8_t *d_raw = nullptr;
+  /* mibayer_set_nr: likewise.  While the frame in the slot is denoised the upload -- or the defect pass -- writes d_nr, one
+   * more mosaic made when the slot first needs one, and the noise reduction pass writes d_src */
+  std::shared_ptr<const mibayer_nr> nr;
+  uint8_t *d_nr = nullptr;
 };
 
 int device_count_cached ()
@@ -363,6 +367,7 @@ struct mibayer_ctx {
   mibayer_hist last_hist;
   std::shared_ptr<const ShadeTable> shading;    /* mibayer_set_shading (NULL: off), under stats_mu */
   std::shared_ptr<const DpcSet> dpc;            /* mibayer_set_dpc (NULL: off), under stats_mu */
+  std::shared_ptr<const mibayer_nr> nr;         /* mibayer_set_nr (NULL: off), under stats_mu */
   uint32_t r2b_lo[2], r2b_hi[2];        /* rgb2bayer v_perm selectors per row parity */
   /* Launch plan: tile shape (kernel variant), XCD band (INT32_MIN = the variant's; MIBAYER_XCD_BAND or
    * mibayer_autotune() set it), store alignment of the generic arm, and where the three came from
@@ -1731,7 +1736,7 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
 {
   if (how == RELEASE_ORPHAN) {
     Wedge *w = c->wedge;
-    for (void *m : { (void *) s.d_src, (void *) s.d_dst, (void *) s.d_stats, (void *) s.d_raw })
+    for (void *m : { (void *) s.d_src, (void *) s.d_dst, (void *) s.d_stats, (void *) s.d_raw, (void *) s.d_nr })
       if (m)
         w->dev_mem.push_back (m);
     if (s.h_stats)
@@ -1769,6 +1774,8 @@ static void free_slot (mibayer_ctx *c, Slot &s, SlotRelease how = RELEASE_CACHE)
     (void) hipFree (s.d_stats);
   if (s.d_raw)
     (void) hipFree (s.d_raw);
+  if (s.d_nr)
+    (void) hipFree (s.d_nr);
   if (s.h_stats)
     mibayer_host_free (s.h_stats);
   if (s.ev_in)
@@ -2257,12 +2264,14 @@ static int slot_take_stats (mibayer_ctx *c, Slot &s)
 {
   std::shared_ptr<const ShadeTable> shade;
   std::shared_ptr<const DpcSet> dpc;
+  std::shared_ptr<const mibayer_nr> nr;
   {
     std::lock_guard<std::mutex> lk (c->stats_mu);
     s.grid = c->stats_grid;
     s.win = c->hist_win;
     shade = c->shading;
     dpc = c->dpc;
+    nr = c->nr;
   }
   s.shade.swap (shade);         /* the slot's old table may go here (hipFree waits for the device): outside the lock */
   shade.reset ();
@@ -2270,6 +2279,12 @@ static int slot_take_stats (mibayer_ctx *c, Slot &s)
   dpc.reset ();
   if (s.dpc && !s.d_raw && hip_failed (hipMalloc ((void **) &s.d_raw, c->src_bytes), "hipMalloc (dpc mosaic)")) {
     s.d_raw = nullptr;
+    (void) hipGetLastError ();
+    return MIBAYER_ERR_NOMEM;
+  }
+  s.nr.swap (nr);
+  if (s.nr && !s.d_nr && hip_failed (hipMalloc ((void **) &s.d_nr, c->src_bytes), "hipMalloc (nr mosaic)")) {
+    s.d_nr = nullptr;
     (void) hipGetLastError ();
     return MIBAYER_ERR_NOMEM;
   }
@@ -2758,9 +2773,149 @@ static int slot_launch_dpc (mibayer_ctx *c, Slot &s, int y0, int y1)
   DpcParams q;
   dpc_params (c, *s.dpc, y0, y1, &q);
   q.src = s.d_raw;
-  q.dst = s.d_src;
+  q.dst = s.nr ? s.d_nr : s.d_src;
   q.src_frame_bytes = q.dst_frame_bytes = c->src_bytes;
   HIP_TRY (launch_dpc (q, 1, c->s_compute));
+  return MIBAYER_OK;
+}
+
+/* ---- noise reduction (group `nr`) ------------------------------------------------------------ */
+
+/* the largest node of a curve at `bits` */
+static int nr_t_max (int bits)
+{
+  const int vmax = (1 << bits) - 1;
+  return bits == 8 ? 255 : vmax < 2047 ? vmax : 2047;
+}
+
+extern "C" int mibayer_set_nr (mibayer_ctx *c, const mibayer_nr *n)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const mibayer_nr> next;
+  if (n) {
+    if (n->struct_size != sizeof (mibayer_nr))
+      return MIBAYER_ERR_ARG;
+    const int t_max = nr_t_max (sample_format (c->cfg).bits);
+    for (int i = 0; i < MIBAYER_NR_NODES; i++)
+      if (n->curve[i] > t_max)
+        return MIBAYER_ERR_ARG;
+    if (c->cfg.width < 6 || c->cfg.height < 5)
+      return MIBAYER_ERR_GEOMETRY;
+    std::shared_ptr<mibayer_nr> t (new (std::nothrow) mibayer_nr (*n));
+    if (!t)
+      return MIBAYER_ERR_NOMEM;
+    t->reserved = 0;
+    next = t;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->nr.swap (next);
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_get_nr (const mibayer_ctx *c, mibayer_nr *out)
+{
+  if (!c || !out || c->inverse)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (!c->nr) {
+    memset (out, 0, sizeof *out);
+    out->struct_size = sizeof *out;
+    return MIBAYER_ERR_EMPTY;
+  }
+  *out = *c->nr;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_nr_curve (int bits, double black, double read_noise, double shot_noise, double strength,
+    mibayer_nr *out)
+{
+  if (!out || (bits != 8 && bits != 10 && bits != 12 && bits != 14 && bits != 16))
+    return MIBAYER_ERR_ARG;
+  for (double v : { black, read_noise, shot_noise, strength })
+    if (!(v >= 0.0) || !std::isfinite (v))
+      return MIBAYER_ERR_ARG;
+  memset (out, 0, sizeof *out);
+  out->struct_size = sizeof *out;
+  const double t_max = nr_t_max (bits);
+  for (int i = 0; i < MIBAYER_NR_NODES; i++) {
+    const double v = (double) (i << (bits - 4));
+    const double over = v - black > 0.0 ? v - black : 0.0;
+    const double t = floor (strength * sqrt (read_noise * read_noise + shot_noise * over) + 0.5);
+    out->curve[i] = (uint16_t) (t < t_max ? t : t_max);
+  }
+  return MIBAYER_OK;
+}
+
+/* the kernel's arguments for curve `n` on context `c`, rows [y0, y1) */
+static void nr_params (const mibayer_ctx *c, const mibayer_nr &n, int y0, int y1, NrParams *q)
+{
+  const mibayer_cfg &f = c->cfg;
+  const SampleFormat sf = sample_format (f);
+  memset (q, 0, sizeof *q);
+  q->width = f.width;
+  q->height = f.height;
+  q->src_stride = q->dst_stride = f.src_stride;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
+  q->shift = sf.bits - 4;
+  q->y0 = y0;
+  q->y1 = y1;
+  for (int k = 0; k < 16; k++) {
+    q->lut[k][0] = n.curve[k];
+    q->lut[k][1] = (int) n.curve[k + 1] - (int) n.curve[k];
+  }
+}
+
+extern "C" int mibayer_nr_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream)
+{
+  if (!c || c->inverse || !d_src || !d_dst || nframes < 0 || d_dst == d_src)
+    return MIBAYER_ERR_ARG;
+  if (nframes > 1 && (src_frame_bytes < c->src_bytes || (src_frame_bytes & 3) || dst_frame_bytes < c->src_bytes
+          || (dst_frame_bytes & 3)))
+    return MIBAYER_ERR_GEOMETRY;
+  if ((((uintptr_t) d_src) & 3) || (((uintptr_t) d_dst) & 3))
+    return MIBAYER_ERR_ARG;
+  std::shared_ptr<const mibayer_nr> t;
+  {
+    std::lock_guard<std::mutex> lk (c->stats_mu);
+    t = c->nr;
+  }
+  if (!t)
+    return MIBAYER_ERR_EMPTY;
+  if (nframes == 0)
+    return MIBAYER_OK;
+  DeviceGuard guard (c->device);
+  if (!guard.ok)
+    return MIBAYER_ERR_HIP;
+  Range r ("mibayer:nr_device");
+  mark_dirty (c, (hipStream_t) hip_stream);
+  NrParams q;
+  nr_params (c, *t, 0, c->cfg.height, &q);
+  q.src = (const uint8_t *) d_src;
+  q.dst = (uint8_t *) d_dst;
+  q.src_frame_bytes = src_frame_bytes;
+  q.dst_frame_bytes = dst_frame_bytes;
+  HIP_TRY (launch_nr (q, nframes, (hipStream_t) hip_stream));
+  return MIBAYER_OK;
+}
+
+/* rows [y0, y1) of the frame in slot `s`, from the mosaic the upload or the defect pass wrote into the one everything
+ * else reads, on the compute queue: behind the defect pass of rows up to y1 + 4 and before the shading pass of the same
+ * rows */
+static int slot_launch_nr (mibayer_ctx *c, Slot &s, int y0, int y1)
+{
+  if (!s.nr || y1 <= y0)
+    return MIBAYER_OK;
+  Range r ("mibayer:nr");
+  NrParams q;
+  nr_params (c, *s.nr, y0, y1, &q);
+  q.src = s.d_nr;
+  q.dst = s.d_src;
+  q.src_frame_bytes = q.dst_frame_bytes = c->src_bytes;
+  HIP_TRY (launch_nr (q, 1, c->s_compute));
   return MIBAYER_OK;
 }
 
@@ -2954,6 +3109,7 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
   const int per = (tiles_y + nb - 1) / nb;
   int uploaded = 0;             /* source rows already queued for upload */
   int final_rows = 0;           /* source rows that have had every pass over the mosaic */
+  int dpc_rows = 0;             /* source rows the defect pass has finished (without one: the rows uploaded) */
   /* the band count follows the plan (choose_host_bands after every plan change) and may have grown since the slot was
    * made: the events a band needs are made when it first needs them (free_slot destroys all kMaxHostBands) */
   for (int b = 0; b < nb; b++) {
@@ -2968,21 +3124,27 @@ static int enqueue_frame_banded (mibayer_ctx *c, Slot &s, const uint8_t *src,
     const int y0 = t0 * th;
     const int y1 = t1 * th < f.height ? t1 * th : f.height;
     /* + the halo row below, and while the frame is corrected the two rows under it that the correction looks at */
-    const int ahead = s.dpc ? halo + 2 : halo;
+    const int ahead = halo + (s.dpc ? 2 : 0) + (s.nr ? 4 : 0);
     const int up_to = y1 + ahead < f.height ? y1 + ahead : f.height;
     /* the rows this band's upload completes: corrected and shaded once, before anything reads them */
-    const int shade_from = s.dpc ? final_rows : uploaded;
-    final_rows = !s.dpc || up_to == f.height ? up_to : up_to - 2;
+    const int shade_from = s.dpc || s.nr ? final_rows : uploaded;
+    const int dpc_from = dpc_rows;
+    dpc_rows = !s.dpc || up_to == f.height ? up_to : up_to - 2;
+    /* ... and denoised once: the rows whose window of four rows below the defect pass has finished */
+    final_rows = !s.nr || up_to == f.height ? dpc_rows : dpc_rows - 4 > final_rows ? dpc_rows - 4 : final_rows;
     if (up_to > uploaded) {
       const size_t off = (size_t) uploaded * f.src_stride;
-      HIP_TRY (hipMemcpyAsync ((s.dpc ? s.d_raw : s.d_src) + off, src + off,
+      HIP_TRY (hipMemcpyAsync ((s.dpc ? s.d_raw : s.nr ? s.d_nr : s.d_src) + off, src + off,
               (size_t) (up_to - uploaded) * f.src_stride, hipMemcpyHostToDevice,
               c->s_h2d));
       uploaded = up_to;
     }
     HIP_TRY (hipEventRecord (s.ev_band_in[b], c->s_h2d));
     HIP_TRY (hipStreamWaitEvent (c->s_compute, s.ev_band_in[b], 0));
-    int rc = slot_launch_dpc (c, s, shade_from, final_rows);
+    int rc = slot_launch_dpc (c, s, dpc_from, dpc_rows);
+    if (rc != MIBAYER_OK)
+      return rc;
+    rc = slot_launch_nr (c, s, shade_from, final_rows);
     if (rc != MIBAYER_OK)
       return rc;
     rc = slot_launch_shade (c, s, shade_from, final_rows);
@@ -3071,7 +3233,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
 {
   {
     Range r ("mibayer:h2d");
-    HIP_TRY (hipMemcpyAsync (s.dpc ? s.d_raw : s.d_src, src, c->src_bytes, hipMemcpyHostToDevice,
+    HIP_TRY (hipMemcpyAsync (s.dpc ? s.d_raw : s.nr ? s.d_nr : s.d_src, src, c->src_bytes, hipMemcpyHostToDevice,
             c->s_h2d));
     HIP_TRY (hipEventRecord (s.ev_in, c->s_h2d));
   }
@@ -3086,6 +3248,9 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
     const int dpc_rc = slot_launch_dpc (c, s, 0, c->cfg.height);
     if (dpc_rc != MIBAYER_OK)
       return dpc_rc;
+    const int nr_rc = slot_launch_nr (c, s, 0, c->cfg.height);
+    if (nr_rc != MIBAYER_OK)
+      return nr_rc;
     const int shade_rc = slot_launch_shade (c, s, 0, c->cfg.height);
     if (shade_rc != MIBAYER_OK)
       return shade_rc;
@@ -3131,10 +3296,10 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   if (rc != MIBAYER_OK)
     return rc;
   const size_t row_bytes = written_row_bytes (c);       /* bytes of a destination row that are written */
-  /* (the captured graphs hold the demosaic launch only: a frame with statistics, shading or defective pixel
-   * correction is launched without them) */
+  /* (the captured graphs hold the demosaic launch only: a frame with statistics, shading, defective pixel
+   * correction or noise reduction is launched without them) */
   const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on
-      && !s.shade && !s.dpc;
+      && !s.shade && !s.dpc && !s.nr;
   /* bands pay when this frame has the link to itself (measured at 4K: +7 %
    * synchronous, -6 % with three frames in flight, which overlap anyway) */
   if (want_graph && c->graph_mode == 1

@@ -411,6 +411,31 @@ struct DpcParams {
  * listed defects of those rows */
 hipError_t launch_dpc (const DpcParams &p, int nframes, hipStream_t stream);
 
+/* Noise reduction (mosaic_nr_kernel; include/mibayer.h, group `nr`): a sigma filter over the 24 same-site neighbours at
+ * +-2 and +-4, from one mosaic into a second one of the same sample format, never in place */
+constexpr int kNrMaxRows = 64;          /* rows a workgroup walks at most */
+constexpr int kNrMinRows = 16;          /* ... and at least, when the launch is too small to fill the device otherwise */
+constexpr int kNrSpread = 1024;         /* workgroups a launch is spread over before the rows per workgroup grow */
+struct NrParams {
+  const uint8_t *src;
+  uint8_t *dst;                 /* never src */
+  unsigned long long src_frame_bytes, dst_frame_bytes;
+  int width, height, src_stride, dst_stride;    /* width >= 6 and even, height >= 5 */
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a dword: identity or a byte swap per 16-bit word (its own inverse) */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  int shift;                    /* depth - 4: a sample's curve interval is S >> shift */
+  int y0, y1;                   /* rows [y0, y1) */
+  int lut[16][2];               /* per interval k: curve[k], curve[k + 1] - curve[k] */
+  /* filled by launch_nr */
+  uint32_t rcp[26];             /* ceil (2^32 / (2 cnt)), cnt = 1 .. 25 */
+  int row_dwords;               /* dwords of a row that hold columns < width (the last one may hold two columns past it) */
+  int seg_rows;                 /* rows a workgroup walks */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row */
+};
+/* one launch over rows [p.y0, p.y1) of `nframes` frames; rows up to four outside that range are read */
+hipError_t launch_nr (const NrParams &p, int nframes, hipStream_t stream);
+
 /* a kernel that only waits, `ms` milliseconds (drills: mibayer_internal_stall) */
 hipError_t launch_stall (int ms, hipStream_t stream);
 

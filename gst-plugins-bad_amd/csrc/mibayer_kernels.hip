@@ -2874,6 +2874,227 @@ hipError_t launch_dpc (const DpcParams &p, int nframes, hipStream_t stream)
 }
 
 /* ------------------------------------------------------------------------- */
+/* noise reduction                                                             */
+/* ------------------------------------------------------------------------- */
+/* out = the rounded mean of S and those of its 24 same-site neighbours at +-2 and +-4 that lie within t (S) of it
+ * (include/mibayer.h, group `nr`).  As in the defect pass everything up to the division is done on dwords that hold two
+ * samples in their 16-bit halves, so one body serves both widths and the 8-bit kernel calls it twice: the differences
+ * saturate, the weight is 0 or 1, and P, N <= 24 * 2047 and cnt <= 25 stay in their halves. */
+
+/* neighbours n against centres s: where |n - s| <= t (t1 = t + 1 per half) n - s goes to P or s - n to N, and cnt counts */
+__device__ __forceinline__ void nr_tap (uint32_t n, uint32_t s, uint32_t t1, uint32_t one, uint32_t &P, uint32_t &N, uint32_t &cnt)
+{
+  const uint32_t dp = dpc_over (n, s), dn = dpc_over (s, n);            /* one of the two is 0 */
+  const uint32_t w = dpc_min (dpc_over (t1, dp | dn), one);
+  P = DPC_U (DPC_V (w) * DPC_V (dp) + DPC_V (P));
+  N = DPC_U (DPC_V (w) * DPC_V (dn) + DPC_V (N));
+  cnt = DPC_U (DPC_V (cnt) + DPC_V (w));
+}
+
+/* t + 1 of one sample: the curve between its nodes k and k + 1 (lut[k] = curve[k], curve[k + 1] - curve[k]), which is
+ * (curve[k] (s - f) + curve[k + 1] f + s / 2) >> sh since curve[k] s is a multiple of s and >> floors */
+__device__ __forceinline__ uint32_t nr_threshold (uint32_t s, const int2 *lut, int sh)
+{
+  const int2 c = lut[s >> sh];
+  const int f = (int) (s & ((1u << sh) - 1u));
+  return (uint32_t) (c.x + ((c.y * f + (1 << (sh - 1))) >> sh)) + 1u;
+}
+
+/* out of one sample: S +- (2 |v| + cnt) / (2 cnt), v = P - N, by the reciprocal (tests/test_nr_model.py proves it exact) */
+__device__ __forceinline__ uint32_t nr_mean (uint32_t s, uint32_t P, uint32_t N, uint32_t cnt, const uint32_t *rcp)
+{
+  const int v = (int) P - (int) N;
+  const uint32_t a = (uint32_t) (v < 0 ? -v : v);
+  const uint32_t q = __umulhi (2u * a + cnt, rcp[cnt]);
+  return v < 0 ? s - q : s + q;
+}
+
+/* r[0 .. 4]: the rows at -4, -2, 0, 2, 4, each as the five dwords of packed halves at -4, -2, 0, 2, 4 columns */
+__device__ __forceinline__ uint32_t nr_samples (const uint32_t (&r)[5][5], const int2 *lut, const uint32_t *rcp, int sh, uint32_t one)
+{
+  const uint32_t s = r[2][2];
+  const uint32_t t1 = nr_threshold (s & 0xffffu, lut, sh) | (nr_threshold (s >> 16, lut, sh) << 16);
+  uint32_t P = 0, N = 0, cnt = 0x00010001u;
+#pragma unroll
+  for (int k = 0; k < 5; k++)
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+      if (k != 2 || j != 2)
+        nr_tap (r[k][j], s, t1, one, P, N, cnt);
+  return nr_mean (s & 0xffffu, P & 0xffffu, N & 0xffffu, cnt & 0xffffu, rcp)
+      | (nr_mean (s >> 16, P >> 16, N >> 16, cnt >> 16, rcp) << 16);
+}
+
+/* The geometry is mosaic_dpc_kernel's: four waves side by side, a lane per dword column, seg_rows rows per workgroup, and
+ * a rolling window in registers, here of nine rows, of which a row uses every other one.  A row of the window is kept as
+ * its five tap dwords -- the samples at -4, -2, 0, +2, +4 columns of the lane's: for a deep mosaic the dwords at -2 .. +2,
+ * unpacked; for an 8-bit one the dwords at -1, 0, +1 and the two byte-aligned pairs between them, still as bytes, split
+ * into even and odd bytes when used (45 registers; the 90 of the unpacked halves would not leave four waves per SIMD).
+ * The row five below is requested before the current row is computed and turned into taps after it.
+ * The borders are substituted at load time.  Rows: the index is reflected about the edge row.  Columns: the lanes at a
+ * row's ends load the dwords inside the row that hold the reflected samples (the dword index reflected likewise; in an
+ * 8-bit row the first lane's left dword is its right one and the last lane's right dword its left one) and a v_perm per
+ * tap, whose selector is the identity in every other lane, puts the reflected samples in place.  A row of an 8-bit mosaic
+ * whose width is 2 mod 4 ends in half a dword: that lane continues its dword with the reflected samples, computes four
+ * and stores two. */
+template <bool IN8>
+__global__ void __launch_bounds__ (256)
+mosaic_nr_kernel (NrParams p)
+{
+  constexpr int NRAW = IN8 ? 3 : 5;
+  __shared__ int2 lut[16];
+  __shared__ uint32_t rcp[32];
+  if (threadIdx.x < 16)
+    lut[threadIdx.x] = make_int2 (p.lut[threadIdx.x][0], p.lut[threadIdx.x][1]);
+  else if (threadIdx.x >= 32 && threadIdx.x < 58)
+    rcp[threadIdx.x - 32] = p.rcp[threadIdx.x - 32];
+  __syncthreads ();
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int ya = p.y0 + (int) blockIdx.y * p.seg_rows;          /* < y1 (launch_nr) */
+  const int yb = ya + p.seg_rows < p.y1 ? ya + p.seg_rows : p.y1;
+  const int g = (int) (strip * 256u + threadIdx.x);             /* dword of the row */
+  if (g >= p.row_dwords)
+    return;
+  const int last = p.row_dwords - 1;                            /* >= 1 (8-bit), >= 2 (deep) */
+  const bool tail = IN8 && 4 * g + 2 >= p.width;                /* columns 4 g + 2, 4 g + 3 are past the row's end */
+  uint32_t one = 0x00010001u;
+  asm ("" : "+v" (one));        /* dpc_any */
+  int idx[NRAW];                /* the dwords loaded, all of them 0 .. last */
+  uint32_t sel[NRAW];           /* the selectors that turn them into taps */
+  constexpr uint32_t kFirst = 0x07060504u;      /* v_perm (a, b, sel): a */
+  if constexpr (IN8) {
+    idx[0] = g > 0 ? g - 1 : g + 1;
+    idx[1] = g;
+    idx[2] = g < last ? g + 1 : g - 1;
+    /* columns -4 .. -1 are columns 4, 3, 2, 1: (a, b) = (dword 1, dword 0) */
+    sel[0] = g > 0 ? kFirst : 0x01020304u;
+    /* the half dword goes on with columns W - 2, W - 3: (a, b) = (itself, the dword left of it) */
+    sel[1] = tail ? 0x03040504u : kFirst;
+    /* (a, b) = (dword idx[2], the lane's own).  The last dword, whole: columns W .. W + 3 are W - 2 .. W - 5; the half
+     * one: W + 2, W + 3 are W - 4, W - 5 of the dword left of it; the one left of the half one: W - 2, W - 1, W - 2, W - 3 */
+    sel[2] = g == last ? (tail ? 0x07060506u : 0x07000102u) : (g == last - 1 && (p.width & 2)) ? 0x03040504u : kFirst;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+      const int d = g + k - 2;
+      idx[k] = d < 0 ? -d : d > last ? 2 * last - d : d;
+    }
+    /* a dword off the left end is (low half of its reflection, high half of the dword right of that), one off the right
+     * end (low half of the dword left of its reflection, high half of the reflection); taps 0, 1, 3, 4 are
+     * v_perm (dword k, its neighbour towards the centre), then comes the byte order */
+    const uint32_t left = 0x03020504u, right = 0x07060100u;
+    const uint32_t base[5] = { g < 2 ? left : kFirst, g < 1 ? left : kFirst, kFirst, g + 1 > last ? right : kFirst,
+      g + 2 > last ? right : kFirst };
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+      sel[k] = __builtin_amdgcn_perm (base[k], base[k], p.in_sel);
+  }
+  const uint8_t *sbase = p.src + frame * p.src_frame_bytes;
+  uint8_t *dcol = p.dst + frame * p.dst_frame_bytes + 4 * (size_t) g;
+  /* row t of the window, -4 <= t < height + 4: rows 0 .. height - 1 of the source only (height >= 5); past the segment's
+   * own halo nothing is needed, and the last row asked for is loaded again */
+  auto load_row = [&] (int t, uint32_t (&raw)[NRAW]) {
+    t = t < yb + 3 ? t : yb + 3;
+    const int r = t < 0 ? -t : t >= p.height ? 2 * (p.height - 1) - t : t;
+    const uint32_t *row = (const uint32_t *) (sbase + (size_t) r * (size_t) p.src_stride);
+#pragma unroll
+    for (int k = 0; k < NRAW; k++)
+      raw[k] = row[idx[k]];
+  };
+  auto taps_of = [&] (const uint32_t (&raw)[NRAW], uint32_t (&w)[5]) {
+    if constexpr (IN8) {
+      const uint32_t c = __builtin_amdgcn_perm (raw[1], raw[0], sel[1]);
+      w[0] = __builtin_amdgcn_perm (raw[0], raw[1], sel[0]);
+      w[4] = __builtin_amdgcn_perm (raw[2], raw[1], sel[2]);
+      w[1] = __builtin_amdgcn_alignbyte (c, w[0], 2);
+      w[2] = c;
+      w[3] = __builtin_amdgcn_alignbyte (w[4], c, 2);
+    } else {
+      w[0] = __builtin_amdgcn_perm (raw[0], raw[1], sel[0]) & p.mask2;
+      w[1] = __builtin_amdgcn_perm (raw[1], raw[2], sel[1]) & p.mask2;
+      w[2] = __builtin_amdgcn_perm (raw[2], raw[2], sel[2]) & p.mask2;
+      w[3] = __builtin_amdgcn_perm (raw[3], raw[2], sel[3]) & p.mask2;
+      w[4] = __builtin_amdgcn_perm (raw[4], raw[3], sel[4]) & p.mask2;
+    }
+  };
+  uint32_t w[9][5], raw[NRAW];
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    load_row (ya - 4 + k, raw);
+    taps_of (raw, w[k]);
+  }
+  for (int y = ya; y < yb; y++) {       /* uniform over the workgroup */
+    load_row (y + 5, raw);
+    uint32_t o;
+    if (IN8) {
+      uint32_t h[5][5];
+#pragma unroll
+      for (int k = 0; k < 5; k++)
+#pragma unroll
+        for (int j = 0; j < 5; j++)
+          h[k][j] = w[2 * k][j] & 0x00ff00ffu;
+      o = nr_samples (h, lut, rcp, p.shift, one);
+#pragma unroll
+      for (int k = 0; k < 5; k++)
+#pragma unroll
+        for (int j = 0; j < 5; j++)
+          h[k][j] = (w[2 * k][j] >> 8) & 0x00ff00ffu;
+      o |= nr_samples (h, lut, rcp, p.shift, one) << 8;
+    } else {
+      const uint32_t h[5][5] = { { w[0][0], w[0][1], w[0][2], w[0][3], w[0][4] }, { w[2][0], w[2][1], w[2][2], w[2][3], w[2][4] },
+        { w[4][0], w[4][1], w[4][2], w[4][3], w[4][4] }, { w[6][0], w[6][1], w[6][2], w[6][3], w[6][4] },
+        { w[8][0], w[8][1], w[8][2], w[8][3], w[8][4] } };
+      o = nr_samples (h, lut, rcp, p.shift, one);
+      o = __builtin_amdgcn_perm (o, o, p.in_sel);
+    }
+    uint8_t *out = dcol + (size_t) y * (size_t) p.dst_stride;
+    if (tail)
+      *(uint16_t *) out = (uint16_t) o;
+    else
+      __builtin_nontemporal_store (o, (uint32_t *) out);
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+#pragma unroll
+      for (int j = 0; j < 5; j++)
+        w[k][j] = w[k + 1][j];
+    taps_of (raw, w[8]);
+  }
+}
+
+hipError_t launch_nr (const NrParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.width < 6 || (p.width & 1) || p.height < 5 || p.y0 < 0 || p.y1 <= p.y0 || p.y1 > p.height || p.dst == p.src
+      || p.shift < 4 || p.shift > 12)
+    return hipErrorInvalidValue;        /* (a reflected row or dword outside the frame) */
+  NrParams q = p;
+  q.rcp[0] = 0;
+  for (uint32_t cnt = 1; cnt <= 25; cnt++)
+    q.rcp[cnt] = (uint32_t) (((1ull << 32) + 2 * cnt - 1) / (2 * cnt));
+  q.row_dwords = p.in8 ? (p.width + 3) / 4 : p.width / 2;
+  const long long strips = (q.row_dwords + 255) / 256;
+  /* rows per workgroup as in launch_dpc */
+  const long long h = p.y1 - p.y0;
+  long long rows = h * strips * nframes / kNrSpread;
+  rows = rows < kNrMinRows ? kNrMinRows : rows > kNrMaxRows ? kNrMaxRows : rows;
+  if ((h + rows - 1) / rows > 65535)
+    rows = (h + 65534) / 65535;
+  const long long gy = (h + rows - 1) / rows;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535)
+    return hipErrorInvalidValue;
+  q.seg_rows = (int) rows;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  const dim3 grid ((unsigned) (strips * nframes), (unsigned) gy);
+  if (p.in8)
+    hipLaunchKernelGGL (mosaic_nr_kernel<true>, grid, dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL (mosaic_nr_kernel<false>, grid, dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

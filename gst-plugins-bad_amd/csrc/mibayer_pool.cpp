@@ -66,6 +66,8 @@
 #pragma weak mibayer_set_shading
 /* ... and the defective pixel correction's: mibayer_pool_set_dpc is refused there too */
 #pragma weak mibayer_set_dpc
+/* ... and the noise reduction's: mibayer_pool_set_nr is refused there too */
+#pragma weak mibayer_set_nr
 
 #include <sched.h>
 
@@ -134,6 +136,7 @@ struct Frame {
   /* mibayer_pool_set_shading: the table the pool held when the frame was accepted (NULL: none), applied like the stage */
   std::shared_ptr<const ShadeSet> shade;
   std::shared_ptr<const DpcAsk> dpc;            /* mibayer_pool_set_dpc: likewise */
+  std::shared_ptr<const mibayer_nr> nr;         /* mibayer_pool_set_nr: likewise */
 };
 
 struct Shard {
@@ -150,6 +153,7 @@ struct Shard {
   std::shared_ptr<const StatsGrid> applied_grid;        /* ... and the statistics grid (NULL: off, as created) */
   std::shared_ptr<const ShadeSet> applied_shade;        /* ... and the shading table (NULL: off, as created) */
   std::shared_ptr<const DpcAsk> applied_dpc;            /* ... and the defective pixel correction (likewise) */
+  std::shared_ptr<const mibayer_nr> applied_nr;         /* ... and the noise reduction curve (likewise) */
   std::atomic<long long> completions { 0 };
   std::atomic<long long> fail_after { -1 };     /* fault injection; -1 = never */
   /* helper thread */
@@ -208,11 +212,21 @@ void apply_dpc (Shard *sh, const Frame *f)
     sh->applied_dpc = f->dpc;
 }
 
+/* the same for the frame's noise reduction curve */
+void apply_nr (Shard *sh, const Frame *f)
+{
+  if (f->nr == sh->applied_nr || !mibayer_set_nr)
+    return;
+  if (mibayer_set_nr (sh->ctx, f->nr.get ()) == MIBAYER_OK)
+    sh->applied_nr = f->nr;
+}
+
 /* the same for the frame's statistics grid (and, with it, the shading table: the two travel together) */
 void apply_stats (Shard *sh, const Frame *f)
 {
   apply_shading (sh, f);
   apply_dpc (sh, f);
+  apply_nr (sh, f);
   if (f->grid == sh->applied_grid || !mibayer_set_stats)
     return;
   const StatsGrid off = {};
@@ -423,6 +437,7 @@ struct mibayer_pool {
   std::shared_ptr<const StatsGrid> last_grid;   /* ... which says what last_zones holds */
   std::shared_ptr<const ShadeSet> shade;        /* mibayer_pool_set_shading: the table of the frames submitted from now on */
   std::shared_ptr<const DpcAsk> dpc;            /* mibayer_pool_set_dpc: likewise */
+  std::shared_ptr<const mibayer_nr> nr;         /* mibayer_pool_set_nr: likewise */
   /* failure report */
   int unreported = 0;
   int failed_device = -1;
@@ -920,6 +935,31 @@ extern "C" int mibayer_pool_set_dpc (mibayer_pool *pool, const mibayer_dpc *dpc)
   return MIBAYER_OK;
 }
 
+/* The noise reduction curve of the frames submitted from now on, kept with each frame like the defect pass's parameters
+ * (apply_nr); the rules are the context layer's (include/mibayer.h), restated on the resolved configuration. */
+extern "C" int mibayer_pool_set_nr (mibayer_pool *pool, const mibayer_nr *nr)
+{
+  if (!pool || !mibayer_set_nr)
+    return MIBAYER_ERR_ARG;
+  if (!nr) {
+    pool->nr.reset ();
+    return MIBAYER_OK;
+  }
+  mibayer_cfg f;
+  if (mibayer_get_cfg (pool->shards[0]->ctx, &f) != MIBAYER_OK || (f.flags & MIBAYER_FLAG_RGB2BAYER)
+      || nr->struct_size != sizeof (mibayer_nr))
+    return MIBAYER_ERR_ARG;
+  const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
+  const int vmax = bits ? (1 << bits) - 1 : 255;
+  for (int i = 0; i < MIBAYER_NR_NODES; i++)
+    if (nr->curve[i] > (vmax < 2047 ? vmax : 2047))
+      return MIBAYER_ERR_ARG;
+  if (f.width < 6 || f.height < 5)
+    return MIBAYER_ERR_GEOMETRY;
+  pool->nr = std::make_shared<mibayer_nr> (*nr);
+  return MIBAYER_OK;
+}
+
 extern "C" int mibayer_pool_inject_stall (mibayer_pool *pool, int shard, int ms)
 {
   if (!pool || shard < 0 || shard >= (int) pool->shards.size ())
@@ -1007,7 +1047,7 @@ extern "C" int mibayer_pool_submit (mibayer_pool *pool, const uint8_t *src,
       sh->stall_ms = 0;
       (void) mibayer_internal_stall (sh->ctx, ms);
     }
-    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {}, pool->shade, pool->dpc };
+    Frame f = { src, dst, tag, (int) idx, (int) idx, F_DIRECT, MIBAYER_OK, false, pool->colour, pool->grid, {}, pool->shade, pool->dpc, pool->nr };
     if (pool->use_helpers && (mibayer_internal_is_pageable (src) || mibayer_internal_is_pageable (dst))
         && !sh->pageable_seen) {
       sh->pageable_seen = true;

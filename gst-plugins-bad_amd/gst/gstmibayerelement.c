@@ -85,7 +85,10 @@ enum
   PROP_SHADING_FILE,
   PROP_DPC_HOT,
   PROP_DPC_COLD,
-  PROP_DEFECT_FILE
+  PROP_DEFECT_FILE,
+  PROP_DENOISE,
+  PROP_NOISE_READ,
+  PROP_NOISE_SHOT
 };
 
 /* bound weakly, like the colour stage's entry points (gstmicolour.h): over a libmibayer without lens shading
@@ -93,6 +96,11 @@ enum
 #pragma weak mibayer_pool_set_shading
 /* ... and over one without defective pixel correction a threshold or a defect-file is */
 #pragma weak mibayer_pool_set_dpc
+/* ... and over one without noise reduction a denoise above 0 is */
+#pragma weak mibayer_pool_set_nr
+#pragma weak mibayer_nr_curve
+
+#define DEFAULT_NOISE_READ 2.0
 
 #define DEFAULT_DEVICE_ID 0
 #define DEFAULT_INFLIGHT 1
@@ -735,6 +743,31 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       return FALSE;
     }
   }
+  if (!inverse && self->act.denoise > 0.0) {
+    /* denoise, noise-read, noise-shot: the curve of the sensor's noise model over the black-level property's value */
+    mibayer_nr nr;
+    const gchar *what = "this libmibayer has no noise reduction";
+
+    rc = MIBAYER_ERR_ARG;
+    if (mibayer_pool_set_nr && mibayer_nr_curve) {
+      what = "mibayer_nr_curve";
+      rc = mibayer_nr_curve (self->src_bits ? self->src_bits : 8, ((GstMiColourProps *) self->act.colour)->black_level,
+          self->act.noise_read, self->act.noise_shot, self->act.denoise, &nr);
+      if (rc == MIBAYER_OK) {
+        what = "mibayer_pool_set_nr";
+        rc = mibayer_pool_set_nr (self->pool, &nr);
+      }
+    }
+    if (rc != MIBAYER_OK) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up noise reduction (denoise=%g noise-read=%g noise-shot=%g)", LABEL (self),
+              self->act.denoise, self->act.noise_read, self->act.noise_shot),
+          g_strdup_printf ("%s: %s", what, mibayer_strerror (rc)));
+      return FALSE;
+    }
+  }
   if (want_colour && ((GstMiColourProps *) self->act.colour)->white_balance == GST_MI_WHITE_BALANCE_GREY_WORLD) {
     guint32 lo, hi;
 
@@ -835,6 +868,15 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
       g_free (self->defect_file);
       self->defect_file = g_value_dup_string (value);
       break;
+    case PROP_DENOISE:
+      self->denoise = g_value_get_double (value);
+      break;
+    case PROP_NOISE_READ:
+      self->noise_read = g_value_get_double (value);
+      break;
+    case PROP_NOISE_SHOT:
+      self->noise_shot = g_value_get_double (value);
+      break;
     default:
       if (gst_mi_colour_set_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -884,6 +926,15 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
       break;
     case PROP_DEFECT_FILE:
       g_value_set_string (value, self->defect_file ? self->defect_file : "");
+      break;
+    case PROP_DENOISE:
+      g_value_set_double (value, self->denoise);
+      break;
+    case PROP_NOISE_READ:
+      g_value_set_double (value, self->noise_read);
+      break;
+    case PROP_NOISE_SHOT:
+      g_value_set_double (value, self->noise_shot);
       break;
     default:
       if (gst_mi_colour_get_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
@@ -1475,6 +1526,9 @@ element_start (GstBaseTransform * base)
   self->act.dpc_cold = self->dpc_cold;
   g_free (self->act.defect_file);
   self->act.defect_file = g_strdup (self->defect_file);
+  self->act.denoise = self->denoise;
+  self->act.noise_read = self->noise_read;
+  self->act.noise_shot = self->noise_shot;
   gst_mi_colour_props_copy (self->act.colour, self->colour);
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
@@ -1593,6 +1647,27 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             "inside the negotiated frame; empty = none", "",
             G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
             G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_DENOISE,
+        g_param_spec_double ("denoise", "Noise reduction strength",
+            "Noise reduction on the mosaic, behind the defective pixel correction "
+            "and before everything else: a sample becomes the mean of those of its "
+            "24 same-colour neighbours (two and four pixels away) that lie within "
+            "this many standard deviations of the noise at its level (noise-read, "
+            "noise-shot, over black-level); 0 = off", 0.0, 1000.0, 0.0,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_NOISE_READ,
+        g_param_spec_double ("noise-read", "Read noise",
+            "Standard deviation of the sensor's read noise, at the depth of the "
+            "mosaic", 0.0, 65535.0, DEFAULT_NOISE_READ,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_NOISE_SHOT,
+        g_param_spec_double ("noise-shot", "Shot noise",
+            "Variance of the sensor's shot noise per level above black-level, at "
+            "the depth of the mosaic", 0.0, 65535.0, 0.0,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
   }
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
@@ -1624,6 +1699,7 @@ gst_mi_bayer_element_instance_setup (GstMiBayerElement * self)
   self->act.timeout_ms = DEFAULT_TIMEOUT_MS;
   self->method = DEFAULT_METHOD;
   self->dpc_hot = self->dpc_cold = self->act.dpc_hot = self->act.dpc_cold = -1;
+  self->noise_read = self->act.noise_read = DEFAULT_NOISE_READ;
   self->act.method = DEFAULT_METHOD;
   self->colour = g_new0 (GstMiColourProps, 1);
   self->act.colour = g_new0 (GstMiColourProps, 1);

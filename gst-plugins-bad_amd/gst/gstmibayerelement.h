@@ -64,6 +64,7 @@ struct _GstMiBayerElement
   gchar *shading_file;          /* lens shading table (bayer2rgb only); NULL or "" = off */
   gint dpc_hot, dpc_cold;       /* defective pixel correction thresholds (bayer2rgb only); -1 = off */
   gchar *defect_file;           /* list of known defects (bayer2rgb only); NULL or "" = none */
+  gdouble denoise, noise_read, noise_shot;      /* noise reduction (bayer2rgb only); denoise 0 = off */
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -80,6 +81,7 @@ struct _GstMiBayerElement
     gchar *shading_file;
     gint dpc_hot, dpc_cold;
     gchar *defect_file;
+    gdouble denoise, noise_read, noise_shot;
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;

@@ -76,6 +76,8 @@ extern "C" {
  * context without a table converts what it converted. */
 /* 5, later additive: defective pixel correction -- struct mibayer_dpc and the entry points of group `dpc`; a context
  * with the correction off converts what it converted. */
+/* 5, later additive: noise reduction -- struct mibayer_nr and the entry points of group `nr`; a context with the curve
+ * off converts what it converted. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -110,6 +112,9 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group nr: noise reduction -- a sigma filter over the 24 same-site neighbours of every sample of the mosaic, its
+ *   threshold a curve over the sample's level, behind the defect pass and before everything else reads the mosaic
+ *     mibayer_set_nr mibayer_get_nr mibayer_nr_device mibayer_pool_set_nr mibayer_nr_curve
  * group dpc: defective pixel correction -- stuck samples of the mosaic, found by threshold against their same-site
  *   neighbours or named in a list, replaced from the flattest neighbour pair before everything else reads them
  *     mibayer_set_dpc mibayer_get_dpc mibayer_dpc_device mibayer_pool_set_dpc
@@ -607,6 +612,70 @@ int mibayer_dpc_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_by
  * frame and handed to a shard's context together with the frame, like the shading table.  Call it from the thread that
  * calls mibayer_pool_submit. */
 int mibayer_pool_set_dpc (mibayer_pool *pool, const mibayer_dpc *dpc);
+
+/* ---- noise reduction (additive within version 5: a struct and the entry points of group `nr`) --------------------- */
+
+/* Spatial noise reduction on the MOSAIC, behind the defect pass and before the shading pass, the statistics, the
+ * histogram and the demosaic read it: the shading gain, the colour matrix and the tone curve amplify what is left, and the
+ * demosaic spreads it over a coloured neighbourhood.  Integers only, bit-exact.
+ *   sample   S at (x, y); depth, max = 2^depth - 1, site, masking and byte order on read and write exactly as in group
+ *            `dpc`
+ *   window   the 24 neighbours of the same site at (x + dx, y + dy), dx, dy in {-4, -2, 0, 2, 4}, not both 0
+ *   border   a coordinate off the frame is reflected about the edge sample: x < 0 -> -x, x >= W -> 2 (W - 1) - x, and
+ *            the same for y with H (numpy.pad mode "reflect").  This keeps the site and, unlike the defect pass's rule,
+ *            replaces a row by one that depends on the row index only.  It needs W >= 6 and H >= 5: a smaller context
+ *            is MIBAYER_ERR_GEOMETRY
+ *   threshold  a curve of MIBAYER_NR_NODES = 17 nodes curve[0 .. 16] over the sample's level, each 0 .. T_MAX, T_MAX = 255
+ *            for an 8-bit mosaic and min (max, 2047) for a deep one.  With sh = depth - 4, s = 1 << sh, k = S >> sh and
+ *            f = S & (s - 1):   t = (curve[k] (s - f) + curve[k + 1] f + (s >> 1)) >> sh
+ *   filter   a neighbour n is included when |n - S| <= t.  P = the sum of n - S over the included n > S, N = the sum of
+ *            S - n over the included n < S (both <= 24 T_MAX < 2^16), cnt = 1 + the number included (1 .. 25),
+ *            v = P - N, q = (2 |v| + cnt) / (2 cnt) rounded down, out = S + q where v >= 0, S - q where v < 0: the mean of
+ *            the included samples and the centre, rounded half away from S.  It lies between the smallest and the
+ *            largest of them: nothing is clamped
+ *   out      a pure function of the SOURCE frame -- neighbours are never filtered values -- which is why the pass cannot
+ *            run in place.  Written as in group `dpc`: only the first W samples of a row, the stride padding of the
+ *            destination keeps what it held.
+ * An all-zero curve is the identity on the masked samples. */
+#define MIBAYER_NR_NODES 17
+typedef struct mibayer_nr {
+  uint32_t struct_size;         /* = sizeof (mibayer_nr) */
+  uint16_t curve[17];           /* thresholds at the levels i << (depth - 4), each 0 .. T_MAX */
+  uint16_t reserved;            /* padding; ignored */
+} mibayer_nr;
+
+/* Sets the curve of a context (NULL: off, the default).  Valid on every bayer2rgb context; MIBAYER_ERR_ARG on an
+ * RGB2BAYER context, a bad struct_size and a node above T_MAX; MIBAYER_ERR_GEOMETRY on a context with W < 6 or H < 5.
+ * It applies to the frames accepted (mibayer_submit / mibayer_process_host) and the mibayer_nr_device calls made after
+ * it returns; frames already accepted keep the curve they were accepted with.  May be called between frames, from any
+ * thread.
+ * HOST PATH: while a curve is set, a ring slot holds one more device mosaic (allocated when first needed, freed with
+ * the slot; three with the defect pass set too): the pass reads what the upload -- or the defect pass -- wrote and writes
+ * the slot's mosaic, each row exactly once (band by band when the frame is launched in bands, four rows behind the rows
+ * the defect pass has finished), before the shading pass -- which then runs in place on denoised samples -- and before
+ * anything else reads it.  While it is set a MIBAYER_FLAG_HIPGRAPH context launches without graphs.  With the curve off
+ * nothing new is called or allocated and the bytes are those of the same context before this entry point existed.
+ * mibayer_process_device[_list] never denoises.
+ * mibayer_get_nr: MIBAYER_ERR_EMPTY when off; else the curve. */
+int mibayer_set_nr (mibayer_ctx *ctx, const mibayer_nr *nr);
+int mibayer_get_nr (const mibayer_ctx *ctx, mibayer_nr *out);
+/* Device path: one batch, `nframes` mosaics denoised with the curve set before, frame f read at d_src + f *
+ * src_frame_bytes (rows of cfg.src_stride bytes) and written at d_dst + f * dst_frame_bytes in the same layout.  Out of
+ * place only: d_dst == d_src is MIBAYER_ERR_ARG, and any other overlap of source and destination is undefined.  The
+ * other errors are those of mibayer_dpc_device; MIBAYER_ERR_EMPTY when the curve is off.  Covered by mibayer_sync when
+ * launched on the context's stream. */
+int mibayer_nr_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, void *d_dst,
+    size_t dst_frame_bytes, int nframes, void *hip_stream);
+/* ... of a pool: the curve of the frames mibayer_pool_submit accepts after it returns (NULL: off), kept with each frame
+ * and handed to a shard's context together with the frame, like the defect pass's parameters.  Call it from the thread
+ * that calls mibayer_pool_submit. */
+int mibayer_pool_set_nr (mibayer_pool *pool, const mibayer_nr *nr);
+/* A curve from a sensor's noise model, host arithmetic in IEEE doubles: node i sits at the level v = i << (depth - 4)
+ * and gets t = floor (strength * sqrt (read_noise^2 + shot_noise * max (v - black, 0)) + 0.5), clamped to T_MAX.
+ * `bits`: 8, 10, 12, 14 or 16; black, read_noise (DN at native depth), shot_noise (DN of variance per DN of signal) and
+ * strength (thresholds per standard deviation) >= 0 and finite, else MIBAYER_ERR_ARG, as are a NULL `out` and any other
+ * depth.  Fills out->struct_size. */
+int mibayer_nr_curve (int bits, double black, double read_noise, double shot_noise, double strength, mibayer_nr *out);
 
 /* ---- global ------------------------------------------------------------- */
 
