@@ -180,6 +180,33 @@ def stats_grey_world(zones, pattern, black=None):
     return rc, tuple(gains)
 
 
+class FocusZone(ctypes.Structure):
+    """struct mibayer_focus_zone (include/mibayer.h): per CFA site s = 2 (y & 1) + (x & 1) of one zone"""
+    _fields_ = [("h", ctypes.c_uint64 * 4), ("v", ctypes.c_uint64 * 4), ("nh", ctypes.c_uint32 * 4),
+                ("nv", ctypes.c_uint32 * 4)]
+
+
+# numpy view of an array of FocusZone
+FOCUS_DTYPE = np.dtype([("h", np.uint64, 4), ("v", np.uint64, 4), ("nh", np.uint32, 4), ("nv", np.uint32, 4)])
+
+
+def focus_score(zones, pattern, colour=1, weights=None):
+    """mibayer_focus_score: (ok, score) from a FOCUS_DTYPE array of zones; colour 0 / 1 / 2 = R / G / B, 3 = all sites;
+    weights: None or one double per zone (no device needed)"""
+    zones = np.ascontiguousarray(zones, FOCUS_DTYPE).reshape(-1)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        assert w.size == zones.size
+    pat = PATTERNS[pattern] if isinstance(pattern, str) else int(pattern)
+    score = ctypes.c_double(-1.0)
+    rc = lib().mibayer_focus_score(_ptr(zones), zones.size, pat, int(colour), None if w is None else _ptr(w),
+                                   ctypes.byref(score))
+    if rc < 0:
+        raise MibayerError(rc, "mibayer_focus_score")
+    return rc, score.value
+
+
 SHADING_MAX_NODES = 129
 
 
@@ -435,6 +462,14 @@ ABI = {
     "mibayer_pool_frame_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "mibayer_stats_grey_world": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_double)]),
+    "mibayer_focus_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_uint32, _vp, _vp]),
+    "mibayer_set_focus": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]),
+    "mibayer_frame_focus": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mibayer_pool_set_focus": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]),
+    "mibayer_pool_frame_focus": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mibayer_focus_score": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
+                                           ctypes.POINTER(ctypes.c_double)]),
     "mibayer_hist_device": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, _vp, _vp]),
     "mibayer_set_hist": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
@@ -587,6 +622,7 @@ class Pool:
         _check(lib().mibayer_pool_create(ctypes.byref(pc), ctypes.byref(self._h)), "mibayer_pool_create")
         self.capacity = lib().mibayer_pool_capacity(self._h)
         self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
+        self._fzones = (1, 1)           # ... and frame_focus(): the last one set_focus() switched on
         if isinstance(deep.get("colour"), Colour):
             self.set_colour(deep["colour"])
 
@@ -614,6 +650,18 @@ class Pool:
         """mibayer_pool_frame_hist: (4, 256) HIST_DTYPE array of the frame wait() handed back last"""
         out = np.zeros(HIST_SHAPE, HIST_DTYPE)
         _check(lib().mibayer_pool_frame_hist(self._h, _ptr(out)), "mibayer_pool_frame_hist")
+        return out
+
+    def set_focus(self, zones_x, zones_y, thr=0):
+        """mibayer_pool_set_focus: focus statistics for the frames submitted from now on; (0, 0) = off"""
+        _check(lib().mibayer_pool_set_focus(self._h, zones_x, zones_y, thr), "mibayer_pool_set_focus")
+        if zones_x and zones_y:
+            self._fzones = (zones_y, zones_x)
+
+    def frame_focus(self):
+        """mibayer_pool_frame_focus: (zones_y, zones_x) FOCUS_DTYPE array of the frame wait() handed back last"""
+        out = np.zeros(self._fzones, FOCUS_DTYPE)
+        _check(lib().mibayer_pool_frame_focus(self._h, _ptr(out), out.size), "mibayer_pool_frame_focus")
         return out
 
     def set_shading(self, shading):
@@ -730,6 +778,7 @@ class Context:
         self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
         self.colour = bool(out.flags & FLAG_COLOUR)
         self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
+        self._fzones = (1, 1)           # ... and frame_focus(): the last one set_focus() switched on
         if isinstance(deep.get("colour"), Colour):
             self.set_colour(deep["colour"])
 
@@ -897,6 +946,56 @@ class Context:
         if not (out[nb:] == 0xA5).all():
             raise AssertionError("mibayer_hist_device wrote past the last histogram")
         return out[:nb].view(HIST_DTYPE).reshape((n,) + HIST_SHAPE)
+
+    # -- mosaic focus statistics ------------------------------------------------------------
+    def focus_device(self, d_src, d_focus, zones_x, zones_y, thr, nframes=1, src_frame_bytes=None, stream="ctx"):
+        """mibayer_focus_device: d_focus receives nframes * zones_y * zones_x FocusZone (96 bytes each)"""
+        s = self.stream if stream == "ctx" else (stream or 0)
+        _check(lib().mibayer_focus_device(self._h, _vp(d_src), src_frame_bytes or self.src_bytes, nframes, zones_x,
+                                          zones_y, thr, _vp(d_focus), _vp(s)), "mibayer_focus_device")
+
+    def set_focus(self, zones_x, zones_y, thr=0):
+        """mibayer_set_focus: focus statistics for the host-path frames accepted from now on; (0, 0) = off"""
+        _check(lib().mibayer_set_focus(self._h, zones_x, zones_y, thr), "mibayer_set_focus")
+        if zones_x and zones_y:
+            self._fzones = (zones_y, zones_x)
+
+    def frame_focus(self):
+        """mibayer_frame_focus: (zones_y, zones_x) FOCUS_DTYPE array of the frame handed back last"""
+        out = np.zeros(self._fzones, FOCUS_DTYPE)
+        _check(lib().mibayer_frame_focus(self._h, _ptr(out), out.size), "mibayer_frame_focus")
+        return out
+
+    def focus_batch_via_device(self, frames, zones_x, zones_y, thr, src_frame_bytes=None, src_offset=0):
+        """frames: (N, ...) on the host, each src_frame_bytes (default: one frame) long -> (N, zones_y, zones_x)
+        FOCUS_DTYPE through ONE mibayer_focus_device launch.  The mosaic starts src_offset bytes into its allocation
+        and is followed by a guard; d_focus is pre-filled with junk and lies between two guards.  All guards, and the
+        mosaic itself, must come back as they went (the kernel is read-only)"""
+        frames = np.ascontiguousarray(frames)
+        n = frames.shape[0]
+        frames = frames.view(np.uint8).reshape(n, -1)
+        pitch = src_frame_bytes or self.src_bytes
+        assert frames.shape[1] == pitch
+        nb = n * zones_x * zones_y * ctypes.sizeof(FocusZone)
+        guard = 256
+        d_src = self.device_alloc(src_offset + n * pitch + guard)
+        d_focus = self.device_alloc(guard + nb + guard)
+        try:
+            self.to_device(d_src + src_offset, frames)
+            self.to_device(d_src + src_offset + n * pitch, np.full(guard, 0x5A, np.uint8))
+            self.to_device(d_focus, np.full(guard + nb + guard, 0xA5, np.uint8))
+            self.focus_device(d_src + src_offset, d_focus + guard, zones_x, zones_y, thr, n, pitch)
+            self.sync()
+            back = self.from_device(d_src + src_offset, n * pitch + guard)
+            out = self.from_device(d_focus, guard + nb + guard)
+        finally:
+            self.device_free(d_src)
+            self.device_free(d_focus)
+        if not (out[:guard] == 0xA5).all() or not (out[guard + nb:] == 0xA5).all():
+            raise AssertionError("mibayer_focus_device wrote outside the focus zones")
+        if not (back[:n * pitch] == frames.reshape(-1)).all() or not (back[n * pitch:] == 0x5A).all():
+            raise AssertionError("mibayer_focus_device changed the mosaic or the bytes behind it")
+        return out[guard:guard + nb].copy().view(FOCUS_DTYPE).reshape(n, zones_y, zones_x)
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):

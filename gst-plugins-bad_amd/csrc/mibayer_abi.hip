@@ -145,6 +145,15 @@ struct HistWin {
   int on = 0, x0 = 0, y0 = 0, w = 0, h = 0;
 };
 
+/* a focus grid and its coring threshold (mibayer_set_focus); zones_x = 0: focus statistics off.  The focus zones of a slot
+ * lie behind its histogram, in the same device and pinned buffers -- which are made that much larger when a slot first
+ * takes a frame with focus on */
+struct FocusGrid {
+  int zones_x = 0, zones_y = 0;
+  uint32_t thr = 0;
+};
+constexpr size_t kFocusSlotBytes = (size_t) MIBAYER_STATS_MAX_ZONES * MIBAYER_STATS_MAX_ZONES * sizeof (mibayer_focus_zone);
+
 constexpr int kMaxHostBands = 8;
 constexpr int kInverseBandUnit = 16;    /* rows; a multiple of every rows-per-block of the rgb2bayer kernel */
 
@@ -202,6 +211,8 @@ struct Slot {
   mibayer_stats_zone *d_stats = nullptr;
   mibayer_stats_zone *h_stats = nullptr;
   HistWin win;                    /* mibayer_set_hist: likewise */
+  FocusGrid fgrid;                /* mibayer_set_focus: likewise */
+  size_t stats_bytes = 0;         /* the size of d_stats and of h_stats */
   /* mibayer_set_shading: the table of the frame in the slot (NULL: none), taken when the frame is accepted like the
    * stage; the reference keeps its device copy alive while the frame's launches may read it */
   std::shared_ptr<const ShadeTable> shade;
@@ -365,6 +376,9 @@ struct mibayer_ctx {
   HistWin hist_win;                     /* mibayer_set_hist / mibayer_frame_hist: likewise, under stats_mu */
   bool last_hist_on = false;
   mibayer_hist last_hist;
+  FocusGrid focus_grid;                 /* mibayer_set_focus / mibayer_frame_focus: likewise, under stats_mu */
+  FocusGrid last_fgrid;
+  std::vector<mibayer_focus_zone> last_focus;
   std::shared_ptr<const ShadeTable> shading;    /* mibayer_set_shading (NULL: off), under stats_mu */
   std::shared_ptr<const DpcSet> dpc;            /* mibayer_set_dpc (NULL: off), under stats_mu */
   std::shared_ptr<const mibayer_nr> nr;         /* mibayer_set_nr (NULL: off), under stats_mu */
@@ -2170,6 +2184,127 @@ extern "C" int mibayer_hist_exposure (const mibayer_hist *hist, int pattern, int
   return 1;
 }
 
+/* ---- mosaic focus statistics (group `focus`) ------------------------------------------- */
+
+static mibayer_focus_zone *slot_focus (mibayer_stats_zone *base)
+{
+  return (mibayer_focus_zone *) ((uint8_t *) base + kStatsSlotBytes + sizeof (mibayer_hist));
+}
+
+/* the argument checks of mibayer_focus_device / mibayer_set_focus (include/mibayer.h) and the kernel's arguments */
+static int focus_params (const mibayer_ctx *c, const FocusGrid &g, FocusParams *q)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  const mibayer_cfg &f = c->cfg;
+  const SampleFormat sf = sample_format (f);
+  if (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1 || g.zones_y > MIBAYER_STATS_MAX_ZONES
+      || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.thr > 2u * (uint32_t) sf.vmax)
+    return MIBAYER_ERR_ARG;
+  memset (q, 0, sizeof *q);
+  q->width = f.width;
+  q->height = f.height;
+  q->src_stride = f.src_stride;
+  q->in8 = sf.in8;
+  q->in_sel = sf.in_sel;
+  q->mask2 = sf.mask2;
+  q->thr = g.thr;
+  q->zones_x = g.zones_x;
+  q->zones_y = g.zones_y;
+  q->ch = 2 * (((f.height + 1) / 2 + g.zones_y - 1) / g.zones_y);     /* as stats_params */
+  q->div_cw = make_fastdiv ((uint32_t) (2 * ((f.width / 2 + g.zones_x - 1) / g.zones_x)));
+  return MIBAYER_OK;
+}
+
+/* zeroes `d_focus` and launches the kernel over `nframes` frames on `stream` */
+static int enqueue_focus (FocusParams &q, const void *d_src, size_t src_frame_bytes, int nframes,
+    mibayer_focus_zone *d_focus, hipStream_t stream)
+{
+  q.src = (const uint8_t *) d_src;
+  q.src_frame_bytes = src_frame_bytes;
+  q.focus = (unsigned long long *) d_focus;
+  const size_t bytes = (size_t) nframes * (size_t) q.zones_x * (size_t) q.zones_y * sizeof (mibayer_focus_zone);
+  HIP_TRY (hipMemsetAsync (d_focus, 0, bytes, stream));
+  HIP_TRY (launch_focus (q, nframes, stream));
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_focus_device (mibayer_ctx *c, const void *d_src, size_t src_frame_bytes, int nframes,
+    int zones_x, int zones_y, uint32_t thr, mibayer_focus_zone *d_focus, void *hip_stream)
+{
+  FocusGrid g;
+  g.zones_x = zones_x;
+  g.zones_y = zones_y;
+  g.thr = thr;
+  return measure_device<FocusParams> (c, d_src, src_frame_bytes, nframes, d_focus, 8, "mibayer:focus_device",
+      hip_stream, [&] (FocusParams *q) { return focus_params (c, g, q); },
+      [&] (FocusParams &q) {
+        return enqueue_focus (q, d_src, src_frame_bytes, nframes, d_focus, (hipStream_t) hip_stream);
+      });
+}
+
+extern "C" int mibayer_set_focus (mibayer_ctx *c, int zones_x, int zones_y, uint32_t thr)
+{
+  if (!c || c->inverse)
+    return MIBAYER_ERR_ARG;
+  FocusGrid g;
+  if (zones_x != 0 || zones_y != 0) {
+    g.zones_x = zones_x;
+    g.zones_y = zones_y;
+    g.thr = thr;
+    FocusParams q;
+    const int rc = focus_params (c, g, &q);
+    if (rc != MIBAYER_OK)
+      return rc;
+  }
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  c->focus_grid = g;
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_frame_focus (mibayer_ctx *c, mibayer_focus_zone *out, int nzones)
+{
+  if (!c || !out)
+    return MIBAYER_ERR_ARG;
+  std::lock_guard<std::mutex> lk (c->stats_mu);
+  if (c->last_fgrid.zones_x == 0)
+    return MIBAYER_ERR_EMPTY;
+  if (nzones != (int) c->last_focus.size ())
+    return MIBAYER_ERR_ARG;
+  memcpy (out, c->last_focus.data (), c->last_focus.size () * sizeof (mibayer_focus_zone));
+  return MIBAYER_OK;
+}
+
+extern "C" int mibayer_focus_score (const mibayer_focus_zone *zones, int nzones, int pattern, int colour,
+    const double *weights, double *score)
+{
+#pragma clang fp contract(off)
+  if (!zones || !score || nzones < 1 || pattern < MIBAYER_BGGR || pattern > MIBAYER_RGGB || colour < 0 || colour > 3)
+    return MIBAYER_ERR_ARG;
+  if (weights)
+    for (int z = 0; z < nzones; z++)
+      if (!(weights[z] >= 0.0) || isinf (weights[z]))
+        return MIBAYER_ERR_ARG;
+  double a = 0.0, n = 0.0;
+  for (int z = 0; z < nzones; z++) {
+    uint64_t az = 0, nz = 0;
+    for (int site = 0; site < 4; site++)
+      if (colour == 3 || kSiteColour[pattern][site] == colour) {
+        az += zones[z].h[site] + zones[z].v[site];
+        nz += (uint64_t) zones[z].nh[site] + zones[z].nv[site];
+      }
+    const double w = weights ? weights[z] : 1.0;
+    const double wa = w * (double) az, wn = w * (double) nz;     /* rounded products: no fused multiply-add */
+    a += wa;
+    n += wn;
+  }
+  *score = 0.0;
+  if (!(n > 0.0))
+    return 0;
+  *score = a / n;
+  return 1;
+}
+
 /* ---- mosaic zone statistics (group `stats`) -------------------------------------------- */
 
 /* the argument checks of mibayer_stats_device / mibayer_set_stats (include/mibayer.h) and the kernel's arguments */
@@ -2269,6 +2404,7 @@ static int slot_take_stats (mibayer_ctx *c, Slot &s)
     std::lock_guard<std::mutex> lk (c->stats_mu);
     s.grid = c->stats_grid;
     s.win = c->hist_win;
+    s.fgrid = c->focus_grid;
     shade = c->shading;
     dpc = c->dpc;
     nr = c->nr;
@@ -2288,12 +2424,22 @@ static int slot_take_stats (mibayer_ctx *c, Slot &s)
     (void) hipGetLastError ();
     return MIBAYER_ERR_NOMEM;
   }
-  if (s.grid.zones_x == 0 && !s.win.on)
+  if (s.grid.zones_x == 0 && !s.win.on && s.fgrid.zones_x == 0)
     return MIBAYER_OK;
-  if (!s.d_stats)
-    HIP_TRY (hipMalloc ((void **) &s.d_stats, kStatsSlotBytes + sizeof (mibayer_hist)));
-  if (!s.h_stats)
-    HIP_TRY (hipHostMalloc ((void **) &s.h_stats, kStatsSlotBytes + sizeof (mibayer_hist), hipHostMallocDefault));
+  const size_t need = kStatsSlotBytes + sizeof (mibayer_hist) + (s.fgrid.zones_x ? kFocusSlotBytes : 0);
+  if (s.stats_bytes < need) {   /* the slot's first measurement, or its first focus zones: the slot is free, nothing
+                                   reads the old buffers */
+    if (s.d_stats)
+      (void) hipFree (s.d_stats);
+    if (s.h_stats)
+      mibayer_host_free (s.h_stats);
+    s.d_stats = nullptr;
+    s.h_stats = nullptr;
+    s.stats_bytes = 0;
+    HIP_TRY (hipMalloc ((void **) &s.d_stats, need));
+    HIP_TRY (hipHostMalloc ((void **) &s.h_stats, need, hipHostMallocDefault));
+    s.stats_bytes = need;
+  }
   return MIBAYER_OK;
 }
 
@@ -2309,6 +2455,16 @@ static int slot_launch_stats (mibayer_ctx *c, Slot &s)
     const int hrc = enqueue_hist (h, s.d_src, c->src_bytes, 1, slot_hist (s.d_stats), c->s_compute);
     if (hrc != MIBAYER_OK)
       return hrc;
+  }
+  if (s.fgrid.zones_x) {
+    FocusParams f;
+    const int rc = focus_params (c, s.fgrid, &f);
+    if (rc != MIBAYER_OK)
+      return rc;
+    Range r ("mibayer:focus");
+    const int frc = enqueue_focus (f, s.d_src, c->src_bytes, 1, slot_focus (s.d_stats), c->s_compute);
+    if (frc != MIBAYER_OK)
+      return frc;
   }
   if (s.grid.zones_x == 0)
     return MIBAYER_OK;
@@ -2326,6 +2482,9 @@ static int slot_download_stats (mibayer_ctx *c, Slot &s)
   if (s.win.on)
     HIP_TRY (hipMemcpyAsync (slot_hist (s.h_stats), slot_hist (s.d_stats), sizeof (mibayer_hist), hipMemcpyDeviceToHost,
             c->s_d2h));
+  if (s.fgrid.zones_x)
+    HIP_TRY (hipMemcpyAsync (slot_focus (s.h_stats), slot_focus (s.d_stats),
+            (size_t) s.fgrid.zones_x * s.fgrid.zones_y * sizeof (mibayer_focus_zone), hipMemcpyDeviceToHost, c->s_d2h));
   if (s.grid.zones_x == 0)
     return MIBAYER_OK;
   HIP_TRY (hipMemcpyAsync (s.h_stats, s.d_stats,
@@ -2340,6 +2499,11 @@ static void slot_retire_stats (mibayer_ctx *c, const Slot &s)
   c->last_hist_on = s.win.on != 0;
   if (s.win.on)
     c->last_hist = *slot_hist (s.h_stats);
+  c->last_fgrid = s.fgrid;
+  if (s.fgrid.zones_x == 0)
+    c->last_focus.clear ();
+  else
+    c->last_focus.assign (slot_focus (s.h_stats), slot_focus (s.h_stats) + (size_t) s.fgrid.zones_x * s.fgrid.zones_y);
   c->last_grid = s.grid;
   if (s.grid.zones_x == 0)
     c->last_zones.clear ();
@@ -3299,7 +3463,7 @@ static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
   /* (the captured graphs hold the demosaic launch only: a frame with statistics, shading, defective pixel
    * correction or noise reduction is launched without them) */
   const bool want_graph = (c->cfg.flags & MIBAYER_FLAG_HIPGRAPH) && !c->inverse && !c->deep && s.grid.zones_x == 0 && !s.win.on
-      && !s.shade && !s.dpc && !s.nr;
+      && s.fgrid.zones_x == 0 && !s.shade && !s.dpc && !s.nr;
   /* bands pay when this frame has the link to itself (measured at 4K: +7 %
    * synchronous, -6 % with three frames in flight, which overlap anyway) */
   if (want_graph && c->graph_mode == 1

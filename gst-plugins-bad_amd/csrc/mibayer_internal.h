@@ -355,6 +355,29 @@ struct HistParams {
 /* one launch over `nframes` frames; p.hist must have been zeroed on the stream before */
 hipError_t launch_hist (const HistParams &p, int nframes, hipStream_t stream);
 
+/* Mosaic focus statistics (mosaic_focus_kernel; include/mibayer.h, group `focus`): read-only over the mosaic, the launch
+ * geometry of mosaic_stats_kernel (segments of kStatsSegRows rows of one zone row) and the five-row window of
+ * mosaic_dpc_kernel, one kernel per sample width, both byte orders */
+struct FocusParams {
+  const uint8_t *src;
+  unsigned long long src_frame_bytes;
+  unsigned long long *focus;    /* nframes x zones_y x zones_x zones of 96 bytes: h[4], v[4] (64-bit), nh[4], nv[4] */
+  int width, height, src_stride;
+  int in8;                      /* 8-bit mosaic: four samples per dword; else two 16-bit words */
+  uint32_t in_sel;              /* v_perm selector on a source dword: identity or a byte swap per 16-bit word */
+  uint32_t mask2;               /* sample mask in both halves of a dword */
+  uint32_t thr;                 /* a response counts when |r| >= thr; <= 2 max */
+  int zones_x, zones_y;
+  int ch;                       /* rows of a zone */
+  FastDiv div_cw;               /* pixels of a zone */
+  /* filled by launch_focus */
+  int row_dwords;               /* dwords of a row that hold columns < width (the last one may hold two columns past it) */
+  int segs;                     /* segments of kStatsSegRows rows per zone row */
+  FastDiv div_strips;           /* workgroups (4 waves x 64 dwords) per row */
+};
+/* one launch over `nframes` frames; p.focus must have been zeroed on the stream before */
+hipError_t launch_focus (const FocusParams &p, int nframes, hipStream_t stream);
+
 /* Lens shading correction (mosaic_shade_kernel; include/mibayer.h, group `shading`): a pointwise pass over the mosaic,
  * in place or into a second mosaic of the same sample format, one kernel per sample width, both byte orders */
 constexpr int kShadeAhead = 8;          /* dword loads in flight per lane = depth of the row loop; even */

@@ -3095,6 +3095,208 @@ hipError_t launch_nr (const NrParams &p, int nframes, hipStream_t stream)
 }
 
 /* ------------------------------------------------------------------------- */
+/* mosaic focus statistics                                                     */
+/* ------------------------------------------------------------------------- */
+/* Per zone and CFA site: sum and number of the same-site second differences |2 S - S(-2) - S(+2)|, across and down, that
+ * reach the threshold (include/mibayer.h, group `focus`).  Read-only over the mosaic.  The launch geometry is
+ * mosaic_stats_kernel's -- four waves side by side, a lane per dword column, one segment of at most kStatsSegRows rows of
+ * ONE zone row per workgroup -- and the stencil is mosaic_dpc_kernel's: a rolling window of the lane's own dword of five
+ * rows, y - 2 .. y + 2, the row three below requested before the current one is computed.  A row arrives as the dwords
+ * left of, at and right of the lane's (three coalesced loads; the neighbours' come from the cache); its horizontal
+ * responses are taken as it arrives and only its own dword enters the window, its vertical ones when it is the window's
+ * middle.  Nothing is substituted at a border: a row index outside the frame and a dword off the row's end are clamped
+ * for the address only, and what does not exist is masked -- `hmask` / `vmask` per 16-bit half of the lane, and `own` /
+ * `vok` per row, uniform over the workgroup.  Rows of another frame are never addressed.
+ * Of a deep mosaic the two samples of a dword are computed in 32 bits (|r| <= 2 * 65535).  Of an 8-bit mosaic a row is
+ * kept as its even and its odd bytes, two samples in the 16-bit halves of a dword as in mosaic_dpc_kernel: |r| <= 510 and
+ * at most kStatsSegRows / 2 rows of one parity fall in a segment, so a half holds the arithmetic (no value leaves its
+ * half: a + b and 2 c are at most 510, max - min borrows nothing) and the sums (32 * 510 < 65536).  The low half is the
+ * lane's first column pair, the high half its second; a pair never straddles two zones.  A lane keeps sum and count per
+ * row parity, column parity (and half) in registers and adds them once into the workgroup's LDS table
+ * [zone column][site], 64-bit for the sums; after a barrier the workgroup issues one global atomic per non-zero entry.
+ * Integer additions: the result does not depend on their order. */
+template <bool IN8>
+__global__ void __launch_bounds__ (256)
+mosaic_focus_kernel (FocusParams p)
+{
+  constexpr int NP = IN8 ? 2 : 1;
+  __shared__ unsigned long long t_h[kStatsMaxZones * 4];
+  __shared__ unsigned long long t_v[kStatsMaxZones * 4];
+  __shared__ uint32_t t_nh[kStatsMaxZones * 4];
+  __shared__ uint32_t t_nv[kStatsMaxZones * 4];
+  const uint32_t frame = fastdiv (blockIdx.x, p.div_strips);
+  const uint32_t strip = blockIdx.x - frame * p.div_strips.d;
+  const int zy = (int) blockIdx.y / p.segs;
+  const int seg = (int) blockIdx.y - zy * p.segs;
+  const int y0 = zy * p.ch + seg * kStatsSegRows;       /* even */
+  int y1 = y0 + kStatsSegRows;
+  y1 = y1 < (zy + 1) * p.ch ? y1 : (zy + 1) * p.ch;
+  y1 = y1 < p.height ? y1 : p.height;
+  if (y0 >= y1)                 /* the whole workgroup: an empty trailing zone row, or a short last segment */
+    return;
+  t_h[threadIdx.x] = 0;
+  t_v[threadIdx.x] = 0;
+  t_nh[threadIdx.x] = 0;
+  t_nv[threadIdx.x] = 0;
+  __syncthreads ();
+
+  const int g = (int) (strip * 256u + threadIdx.x);     /* dword of the row */
+  if (g < p.row_dwords) {
+    const int last = p.row_dwords - 1;
+    const int x0 = IN8 ? 4 * g : 2 * g;                 /* its first column: even, < width */
+    const bool tail = IN8 && x0 + 2 >= p.width;         /* columns x0 + 2, x0 + 3 are past the row's end */
+    const int gl = g > 0 ? g - 1 : g, gr = g < last ? g + 1 : g;        /* 0 .. last: for the address only */
+    /* the halves of the lane that have both horizontal neighbours / that exist.  8-bit: the first pair needs columns
+     * x0 - 2 and x0 + 2, the second x0 + 4; deep: both columns need dwords g - 1 and g + 1 */
+    const uint32_t hmask = IN8 ? (g > 0 && !tail ? 0xffffu : 0u) | (g < last ? 0xffff0000u : 0u)
+        : g > 0 && g < last ? 0xffffffffu : 0u;
+    const uint32_t vmask = tail ? 0xffffu : 0xffffffffu;
+    const uint32_t thr2 = p.thr * 0x10001u;             /* 8-bit: thr <= 510 in both halves */
+    uint32_t one = 0x00010001u;
+    asm ("" : "+v" (one));      /* dpc_any */
+    const uint8_t *sbase = p.src + frame * p.src_frame_bytes;
+    /* [row parity][column parity] */
+    uint32_t sh[2][2] = {}, sv[2][2] = {}, nh[2][2] = {}, nv[2][2] = {};
+    /* row t of the window, y0 - 2 <= t: rows 0 .. height - 1 of this frame only; past the segment's own halo nothing is
+     * needed, and the last row asked for is loaded again */
+    auto load_row = [&] (int t, uint32_t (&raw)[3]) {
+      t = t < y1 + 1 ? t : y1 + 1;
+      const int r = t < 0 ? 0 : t >= p.height ? p.height - 1 : t;
+      const uint32_t *row = (const uint32_t *) (sbase + (size_t) r * (size_t) p.src_stride);
+      raw[0] = row[gl];
+      raw[1] = row[g];
+      raw[2] = row[gr];
+    };
+    /* |2 c - a - b| >= thr where `valid`: added to sum[k] and counted in num[k]; a, c, b hold column parity k.  8-bit: in
+     * both halves at once; deep: one sample in 32 bits */
+    auto add = [&] (uint32_t a, uint32_t c, uint32_t b, uint32_t valid, uint32_t &sum, uint32_t &num) {
+      if (IN8) {
+        const uint32_t x = c << 1, y = a + b;
+        const uint32_t d = dpc_max (x, y) - dpc_min (x, y);
+        const uint32_t m = dpc_any (dpc_over (d + 0x00010001u, thr2), one) & valid;
+        sum += d & m;
+        num += m & 0x00010001u;
+      } else {
+        const int r = 2 * (int) c - (int) a - (int) b;
+        const uint32_t d = (uint32_t) (r < 0 ? -r : r);
+        const bool in = valid && d >= p.thr;
+        sum += in ? d : 0u;
+        num += in ? 1u : 0u;
+      }
+    };
+    /* the row that arrives, of parity rp: its own dword into window row `c`, and -- a row of the segment -- its
+     * horizontal responses */
+    auto arrive = [&] (const uint32_t (&raw)[3], uint32_t (&c)[NP], int rp, bool own) {
+      const uint32_t valid = own ? hmask : 0u;
+      if (IN8) {
+        const uint32_t l = __builtin_amdgcn_alignbyte (raw[1], raw[0], 2), r = __builtin_amdgcn_alignbyte (raw[2], raw[1], 2);
+        c[0] = raw[1] & 0x00ff00ffu;
+        c[NP - 1] = (raw[1] >> 8) & 0x00ff00ffu;
+        add (l & 0x00ff00ffu, c[0], r & 0x00ff00ffu, valid, sh[rp][0], nh[rp][0]);
+        add ((l >> 8) & 0x00ff00ffu, c[NP - 1], (r >> 8) & 0x00ff00ffu, valid, sh[rp][1], nh[rp][1]);
+      } else {
+        const uint32_t l = __builtin_amdgcn_perm (raw[0], raw[0], p.in_sel) & p.mask2;
+        const uint32_t r = __builtin_amdgcn_perm (raw[2], raw[2], p.in_sel) & p.mask2;
+        c[0] = __builtin_amdgcn_perm (raw[1], raw[1], p.in_sel) & p.mask2;
+        add (l & 0xffffu, c[0] & 0xffffu, r & 0xffffu, valid, sh[rp][0], nh[rp][0]);
+        add (l >> 16, c[0] >> 16, r >> 16, valid, sh[rp][1], nh[rp][1]);
+      }
+    };
+    uint32_t w[5][NP], raw[3];
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+      load_row (y0 - 2 + k, raw);
+      arrive (raw, w[k], k & 1, k >= 2 && y0 - 2 + k < y1);
+    }
+    /* row y, of parity rp, is the middle of the window */
+    auto step = [&] (int y, int rp) {
+      load_row (y + 3, raw);
+      const uint32_t valid = y >= 2 && y + 2 < p.height ? vmask : 0u;
+      if (IN8) {
+        add (w[0][0], w[2][0], w[4][0], valid, sv[rp][0], nv[rp][0]);
+        add (w[0][NP - 1], w[2][NP - 1], w[4][NP - 1], valid, sv[rp][1], nv[rp][1]);
+      } else {
+        add (w[0][0] & 0xffffu, w[2][0] & 0xffffu, w[4][0] & 0xffffu, valid, sv[rp][0], nv[rp][0]);
+        add (w[0][0] >> 16, w[2][0] >> 16, w[4][0] >> 16, valid, sv[rp][1], nv[rp][1]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int j = 0; j < NP; j++)
+          w[k][j] = w[k + 1][j];
+      arrive (raw, w[4], rp ^ 1, y + 3 < y1);
+    };
+    for (int y = y0; y < y1; y += 2) {  /* uniform over the workgroup; y0 is even: the parities are constants */
+      step (y, 0);
+      if (y + 1 < y1)
+        step (y + 1, 1);
+    }
+#pragma unroll
+    for (int pr = 0; pr < NP; pr++) {   /* the lane's column pairs */
+      if (pr == 1 && tail)
+        continue;
+      const uint32_t zx = fastdiv ((uint32_t) (x0 + 2 * pr), p.div_cw);
+#pragma unroll
+      for (int site = 0; site < 4; site++) {
+        const uint32_t e = zx * 4u + (uint32_t) site;
+        const int rp = site >> 1, k = site & 1;
+        const uint32_t a = IN8 ? (sh[rp][k] >> (16 * pr)) & 0xffffu : sh[rp][k];
+        const uint32_t na = IN8 ? (nh[rp][k] >> (16 * pr)) & 0xffffu : nh[rp][k];
+        const uint32_t b = IN8 ? (sv[rp][k] >> (16 * pr)) & 0xffffu : sv[rp][k];
+        const uint32_t nb = IN8 ? (nv[rp][k] >> (16 * pr)) & 0xffffu : nv[rp][k];
+        if (na) {
+          atomicAdd (&t_h[e], (unsigned long long) a);
+          atomicAdd (&t_nh[e], na);
+        }
+        if (nb) {
+          atomicAdd (&t_v[e], (unsigned long long) b);
+          atomicAdd (&t_nv[e], nb);
+        }
+      }
+    }
+  }
+  __syncthreads ();
+  /* thread t owns table entry t = zone column t / 4, site t % 4 (columns >= zones_x were never added to); a zone is
+   * h[4], v[4] (64-bit), nh[4], nv[4] */
+  const uint32_t e = threadIdx.x;
+  unsigned long long *zone = p.focus
+      + 12ull * (((unsigned long long) frame * (uint32_t) p.zones_y + (uint32_t) zy) * (uint32_t) p.zones_x + (e >> 2));
+  if (t_nh[e]) {
+    atomicAdd (zone + (e & 3u), t_h[e]);
+    atomicAdd ((uint32_t *) (zone + 8) + (e & 3u), t_nh[e]);
+  }
+  if (t_nv[e]) {
+    atomicAdd (zone + 4 + (e & 3u), t_v[e]);
+    atomicAdd ((uint32_t *) (zone + 10) + (e & 3u), t_nv[e]);
+  }
+}
+
+hipError_t launch_focus (const FocusParams &p, int nframes, hipStream_t stream)
+{
+  if (nframes <= 0)
+    return nframes == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (p.width < 2 || (p.width & 1) || p.height < 1 || p.zones_x < 1 || p.zones_x > kStatsMaxZones || p.zones_y < 1
+      || p.ch < 2 || (p.ch & 1) || p.div_cw.d < 2 || (p.div_cw.d & 1)
+      || (unsigned long long) p.div_cw.d * (unsigned) p.zones_x < (unsigned) p.width
+      || (long long) p.ch * p.zones_y < p.height || (p.in8 && p.thr > 510u))
+    return hipErrorInvalidValue;        /* (a zone column past the LDS table, a pair across two zones, a threshold past a half) */
+  FocusParams q = p;
+  q.row_dwords = p.in8 ? (p.width + 3) / 4 : p.width / 2;
+  q.segs = (p.ch + kStatsSegRows - 1) / kStatsSegRows;
+  const long long strips = (q.row_dwords + 255) / 256;
+  const long long gy = (long long) q.segs * p.zones_y;
+  if (strips * nframes > 0x7fffffffLL || gy > 65535)
+    return hipErrorInvalidValue;
+  q.div_strips = make_fastdiv ((uint32_t) strips);
+  const dim3 grid ((unsigned) (strips * nframes), (unsigned) gy);
+  if (p.in8)
+    hipLaunchKernelGGL (mosaic_focus_kernel<true>, grid, dim3 (256), 0, stream, q);
+  else
+    hipLaunchKernelGGL (mosaic_focus_kernel<false>, grid, dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* stall drill                                                                 */
 /* ------------------------------------------------------------------------- */
 /* One wave that does nothing for `ticks` ticks of the 100 MHz wall clock: occupies a queue the way a device that

@@ -62,6 +62,9 @@
 /* ... and the histogram's: mibayer_pool_set_hist is refused there too */
 #pragma weak mibayer_set_hist
 #pragma weak mibayer_frame_hist
+/* ... and the focus statistics': mibayer_pool_set_focus is refused there too */
+#pragma weak mibayer_set_focus
+#pragma weak mibayer_frame_focus
 /* ... and the shading table's: mibayer_pool_set_shading is refused there too */
 #pragma weak mibayer_set_shading
 /* ... and the defective pixel correction's: mibayer_pool_set_dpc is refused there too */
@@ -86,11 +89,14 @@
 
 namespace {
 
-/* what mibayer_pool_set_stats and mibayer_pool_set_hist asked for, together: one record per frame carries both */
+/* what mibayer_pool_set_stats, mibayer_pool_set_hist and mibayer_pool_set_focus asked for, together: one record per
+ * frame carries all three */
 struct StatsGrid {
   int zones_x, zones_y;         /* (0, 0): no zones */
   uint32_t lo, hi;
   int hist, x0, y0, w, h;       /* hist = 0: no histogram */
+  int fzones_x, fzones_y;       /* (0, 0): no focus zones */
+  uint32_t thr;
 };
 /* what mibayer_pool_set_shading asked for: the parameters and the pool's copy of the table (par.table points into it) */
 struct ShadeSet {
@@ -104,6 +110,11 @@ struct DpcAsk {
 };
 /* a frame's histogram rides behind its zones in the same vector, as it does in a context's slot */
 constexpr size_t kHistZones = sizeof (mibayer_hist) / sizeof (mibayer_stats_zone);
+/* ... and its focus zones behind the histogram, in as many elements of the vector as hold them */
+inline size_t focus_span (size_t nf)
+{
+  return (nf * sizeof (mibayer_focus_zone) + sizeof (mibayer_stats_zone) - 1) / sizeof (mibayer_stats_zone);
+}
 
 enum FrameState {
   F_DIRECT,     /* in the ring of its shard's context, submitted by the streaming thread */
@@ -234,21 +245,27 @@ void apply_stats (Shard *sh, const Frame *f)
   bool ok = mibayer_set_stats (sh->ctx, g->zones_x, g->zones_y, g->lo, g->hi) == MIBAYER_OK;
   if (mibayer_set_hist)
     ok = mibayer_set_hist (sh->ctx, g->hist, g->x0, g->y0, g->w, g->h) == MIBAYER_OK && ok;
+  if (mibayer_set_focus)
+    ok = mibayer_set_focus (sh->ctx, g->fzones_x, g->fzones_y, g->thr) == MIBAYER_OK && ok;
   if (ok)
     sh->applied_grid = f->grid;
 }
 
-/* the zones, then the histogram, of the frame the context of `sh` handed back last; empty when it has neither */
+/* the zones, then the histogram, then the focus zones of the frame the context of `sh` handed back last; empty when it has neither */
 void read_stats (Shard *sh, const StatsGrid *g, std::vector<mibayer_stats_zone> *z)
 {
   z->clear ();
   if (!g || !mibayer_frame_stats)
     return;
   const size_t nz = (size_t) g->zones_x * (size_t) g->zones_y;
-  z->resize (nz + (g->hist ? kHistZones : 0));
+  const size_t nh = g->hist ? kHistZones : 0, nf = (size_t) g->fzones_x * (size_t) g->fzones_y;
+  z->resize (nz + nh + focus_span (nf));
   bool ok = nz == 0 || mibayer_frame_stats (sh->ctx, z->data (), (int) nz) == MIBAYER_OK;
   if (g->hist)
     ok = ok && mibayer_frame_hist && mibayer_frame_hist (sh->ctx, (mibayer_hist *) (z->data () + nz)) == MIBAYER_OK;
+  if (nf)
+    ok = ok && mibayer_frame_focus
+        && mibayer_frame_focus (sh->ctx, (mibayer_focus_zone *) (z->data () + nz + nh), (int) nf) == MIBAYER_OK;
   if (!ok)
     z->clear ();
 }
@@ -777,12 +794,14 @@ extern "C" int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour
 
 /* The statistics grid of the frames submitted from now on, kept with each frame like the colour stage (apply_stats);
  * the range checks are the context layer's: the grid is tried on the first shard's context -- whose own frames carry
- * theirs, and get it back before they are handed over -- so a bad one is refused here and not frames later.  Both
- * setters end here: `g` is what the frames submitted from now on get (neither zones nor a histogram: NULL), and
- * `hist_call` says which half of it is new. */
-static int pool_set_grid (mibayer_pool *pool, const StatsGrid &g, bool hist_call)
+ * theirs, and get it back before they are handed over -- so a bad one is refused here and not frames later.  The three
+ * setters end here: `g` is what the frames submitted from now on get (no zones, histogram or focus zones: NULL), and
+ * `which` says which part of it is new. */
+enum { SET_STATS, SET_HIST, SET_FOCUS };
+static int pool_set_grid (mibayer_pool *pool, const StatsGrid &g, int which)
 {
-  if (g.zones_x == 0 && g.zones_y == 0 && !g.hist) {
+  const bool hist_call = which == SET_HIST;
+  if (g.zones_x == 0 && g.zones_y == 0 && !g.hist && g.fzones_x == 0 && g.fzones_y == 0) {
     pool->grid.reset ();
     return MIBAYER_OK;
   }
@@ -794,11 +813,12 @@ static int pool_set_grid (mibayer_pool *pool, const StatsGrid &g, bool hist_call
     }
   if (probe) {
     const int rc = hist_call ? mibayer_set_hist (probe->ctx, g.hist, g.x0, g.y0, g.w, g.h)
+        : which == SET_FOCUS ? mibayer_set_focus (probe->ctx, g.fzones_x, g.fzones_y, g.thr)
         : mibayer_set_stats (probe->ctx, g.zones_x, g.zones_y, g.lo, g.hi);
     if (rc != MIBAYER_OK)
       return rc;
     pool->grid = std::make_shared<const StatsGrid> (g);
-    probe->applied_grid = std::make_shared<const StatsGrid> (g);        /* no frame's: apply_stats sets both halves */
+    probe->applied_grid = std::make_shared<const StatsGrid> (g);        /* no frame's: apply_stats sets every part */
     return MIBAYER_OK;
   }
   /* every context is driven by a helper thread: the same rule on the resolved configuration */
@@ -807,7 +827,11 @@ static int pool_set_grid (mibayer_pool *pool, const StatsGrid &g, bool hist_call
     return MIBAYER_ERR_ARG;
   const int bits = (int) ((f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8);
   const uint32_t vmax = bits ? (1u << bits) - 1u : 255u;
-  if (!hist_call && (g.zones_x | g.zones_y) && (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1
+  if (which == SET_FOCUS && (g.fzones_x | g.fzones_y) && (g.fzones_x < 1 || g.fzones_x > MIBAYER_STATS_MAX_ZONES
+          || g.fzones_y < 1 || g.fzones_y > MIBAYER_STATS_MAX_ZONES || g.fzones_x > f.width / 2
+          || g.fzones_y > f.height / 2 || g.thr > 2 * vmax))
+    return MIBAYER_ERR_ARG;
+  if (which == SET_STATS && (g.zones_x | g.zones_y) && (g.zones_x < 1 || g.zones_x > MIBAYER_STATS_MAX_ZONES || g.zones_y < 1
           || g.zones_y > MIBAYER_STATS_MAX_ZONES || g.zones_x > f.width / 2 || g.zones_y > f.height / 2 || g.lo > g.hi
           || g.hi > vmax))
     return MIBAYER_ERR_ARG;
@@ -828,7 +852,7 @@ extern "C" int mibayer_pool_set_stats (mibayer_pool *pool, int zones_x, int zone
   g.zones_y = zones_y;
   g.lo = lo;
   g.hi = hi;
-  return pool_set_grid (pool, g, false);
+  return pool_set_grid (pool, g, SET_STATS);
 }
 
 extern "C" int mibayer_pool_frame_stats (mibayer_pool *pool, mibayer_stats_zone *out, int nzones)
@@ -854,7 +878,7 @@ extern "C" int mibayer_pool_set_hist (mibayer_pool *pool, int on, int x0, int y0
   g.y0 = on ? y0 : 0;
   g.w = on ? w : 0;
   g.h = on ? h : 0;
-  return pool_set_grid (pool, g, true);
+  return pool_set_grid (pool, g, SET_HIST);
 }
 
 extern "C" int mibayer_pool_frame_hist (mibayer_pool *pool, mibayer_hist *out)
@@ -863,7 +887,34 @@ extern "C" int mibayer_pool_frame_hist (mibayer_pool *pool, mibayer_hist *out)
     return MIBAYER_ERR_ARG;
   if (!pool->has_zones || !pool->last_grid->hist)
     return MIBAYER_ERR_EMPTY;
-  memcpy (out, pool->last_zones.data () + pool->last_zones.size () - kHistZones, sizeof *out);
+  memcpy (out, pool->last_zones.data () + (size_t) pool->last_grid->zones_x * pool->last_grid->zones_y, sizeof *out);
+  return MIBAYER_OK;
+}
+
+/* The focus grid of the frames submitted from now on: kept, applied and fetched with the statistics grid */
+extern "C" int mibayer_pool_set_focus (mibayer_pool *pool, int zones_x, int zones_y, uint32_t thr)
+{
+  if (!pool || !mibayer_set_stats || !mibayer_frame_stats || !mibayer_set_focus || !mibayer_frame_focus)
+    return MIBAYER_ERR_ARG;
+  StatsGrid g = pool->grid ? *pool->grid : StatsGrid ();
+  const bool on = zones_x != 0 || zones_y != 0;
+  g.fzones_x = zones_x;
+  g.fzones_y = zones_y;
+  g.thr = on ? thr : 0;
+  return pool_set_grid (pool, g, SET_FOCUS);
+}
+
+extern "C" int mibayer_pool_frame_focus (mibayer_pool *pool, mibayer_focus_zone *out, int nzones)
+{
+  if (!pool || !out)
+    return MIBAYER_ERR_ARG;
+  if (!pool->has_zones || pool->last_grid->fzones_x == 0)
+    return MIBAYER_ERR_EMPTY;
+  if (nzones != pool->last_grid->fzones_x * pool->last_grid->fzones_y)
+    return MIBAYER_ERR_ARG;
+  const size_t before = (size_t) pool->last_grid->zones_x * pool->last_grid->zones_y
+      + (pool->last_grid->hist ? kHistZones : 0);
+  memcpy (out, pool->last_zones.data () + before, (size_t) nzones * sizeof (mibayer_focus_zone));
   return MIBAYER_OK;
 }
 

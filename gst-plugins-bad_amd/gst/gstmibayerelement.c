@@ -88,7 +88,10 @@ enum
   PROP_DEFECT_FILE,
   PROP_DENOISE,
   PROP_NOISE_READ,
-  PROP_NOISE_SHOT
+  PROP_NOISE_SHOT,
+  PROP_FOCUS_ZONES_X,
+  PROP_FOCUS_ZONES_Y,
+  PROP_FOCUS_THRESHOLD
 };
 
 /* bound weakly, like the colour stage's entry points (gstmicolour.h): over a libmibayer without lens shading
@@ -99,6 +102,10 @@ enum
 /* ... and over one without noise reduction a denoise above 0 is */
 #pragma weak mibayer_pool_set_nr
 #pragma weak mibayer_nr_curve
+/* ... and over one without focus statistics a focus grid is */
+#pragma weak mibayer_pool_set_focus
+#pragma weak mibayer_pool_frame_focus
+#pragma weak mibayer_focus_score
 
 #define DEFAULT_NOISE_READ 2.0
 
@@ -211,8 +218,12 @@ element_post_notes (GstMiBayerElement * self)
   gchar *note, *text, *debug;
   GQuark domain;
   gint code;
+  GQueue focus = G_QUEUE_INIT;
+  GstStructure *s;
 
   g_mutex_lock (&self->flow_lock);
+  while ((s = g_queue_pop_head (&self->focus_notes)) != NULL)
+    g_queue_push_tail (&focus, s);
   note = self->failure_note;
   self->failure_note = NULL;
   text = self->error_text;
@@ -221,6 +232,8 @@ element_post_notes (GstMiBayerElement * self)
   code = self->error_code;
   self->error_text = self->error_debug = NULL;
   g_mutex_unlock (&self->flow_lock);
+  while ((s = g_queue_pop_head (&focus)) != NULL)       /* one per frame collected, in order */
+    gst_element_post_message (GST_ELEMENT (self), gst_message_new_element (GST_OBJECT (self), s));
   if (text != NULL)             /* takes ownership of both strings */
     gst_element_message_full (GST_ELEMENT (self), GST_MESSAGE_ERROR, domain,
         code, text, debug, __FILE__, GST_FUNCTION, __LINE__);
@@ -258,6 +271,43 @@ element_abandon_quarantine_locked (GstMiBayerElement * self)
         g_queue_get_length (&self->quarantine));
     g_queue_clear (&self->quarantine);
   }
+}
+
+/* focus-zones-x/-y (flow_lock held): the focus zones of the frame the pool has just handed back become one
+ * `mibayer-focus` element message, posted by element_post_notes */
+static void
+element_note_focus_locked (GstMiBayerElement * self)
+{
+  const gint zx = self->act.focus_zones_x, zy = self->act.focus_zones_y, n = zx * zy;
+  mibayer_focus_zone *zones = g_new0 (mibayer_focus_zone, n);
+  GValue scores = G_VALUE_INIT, one = G_VALUE_INIT;
+  gdouble score = 0.0;
+  GstStructure *s;
+  gint z;
+
+  if (mibayer_pool_frame_focus (self->pool, zones, n) != MIBAYER_OK) {
+    g_free (zones);             /* (a frame converted before the grid was set: none today) */
+    return;
+  }
+  g_value_init (&scores, GST_TYPE_ARRAY);
+  g_value_init (&one, G_TYPE_DOUBLE);
+  for (z = 0; z < n; z++) {
+    gdouble zs = 0.0;
+
+    if (mibayer_focus_score (&zones[z], 1, self->format, 1, NULL, &zs) != 1)
+      zs = 0.0;
+    g_value_set_double (&one, zs);
+    gst_value_array_append_value (&scores, &one);
+  }
+  if (mibayer_focus_score (zones, n, self->format, 1, NULL, &score) != 1)
+    score = 0.0;
+  s = gst_structure_new ("mibayer-focus", "frame", G_TYPE_UINT64, self->focus_frame++, "zones-x", G_TYPE_INT, zx,
+      "zones-y", G_TYPE_INT, zy, "threshold", G_TYPE_UINT, self->act.focus_threshold, "score", G_TYPE_DOUBLE, score,
+      NULL);
+  gst_structure_take_value (s, "zone-scores", &scores);
+  g_value_unset (&one);
+  g_free (zones);
+  g_queue_push_tail (&self->focus_notes, s);
 }
 
 /* oldest frame (flow_lock held): wait for the GPU, unmap, hand the output buffer
@@ -321,6 +371,8 @@ element_collect_locked (GstMiBayerElement * self, GstBuffer ** outbuf,
         && gst_mi_awb_step (self->act.colour, (GstMiAwb *) self->awb_gain, &zone, self->format, &colour))
       (void) mibayer_pool_set_colour (self->pool, &colour);
   }
+  if (self->focus_on)
+    element_note_focus_locked (self);
   *outbuf = p->outbuf;
   *owned = p->owns_outbuf;
   pending_release (p, TRUE);
@@ -644,6 +696,7 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
   self->capacity = 0;
   self->awb_on = FALSE;
   self->ae_on = FALSE;
+  self->focus_on = FALSE;
 
   /* the colour stage: only when a colour property is off its default (the default output is the reference's bytes) */
   want_colour = !inverse && !gst_mi_colour_props_are_default (self->act.colour);
@@ -804,6 +857,21 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
     self->ae_e = 1.0;
     self->ae_on = TRUE;
   }
+  if (!inverse && self->act.focus_zones_x > 0 && self->act.focus_zones_y > 0) {
+    rc = mibayer_pool_set_focus && mibayer_pool_frame_focus && mibayer_focus_score
+        ? mibayer_pool_set_focus (self->pool, self->act.focus_zones_x, self->act.focus_zones_y,
+        self->act.focus_threshold) : MIBAYER_ERR_ARG;
+    if (rc != MIBAYER_OK) {
+      mibayer_pool_destroy (self->pool);
+      self->pool = NULL;
+      element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
+          g_strdup_printf ("%s: cannot set up focus statistics (focus-zones-x=%d focus-zones-y=%d focus-threshold=%u)",
+              LABEL (self), self->act.focus_zones_x, self->act.focus_zones_y, self->act.focus_threshold),
+          g_strdup_printf ("mibayer_pool_set_focus: %s", mibayer_strerror (rc)));
+      return FALSE;
+    }
+    self->focus_on = TRUE;
+  }
   /* a GPU that stops answering is dropped like one that reports an error, after this long */
   (void) mibayer_pool_set_wait_timeout (self->pool, self->act.timeout_ms);
   self->pool_stride = video_stride;
@@ -877,6 +945,15 @@ element_set_property (GObject * object, guint prop_id, const GValue * value,
     case PROP_NOISE_SHOT:
       self->noise_shot = g_value_get_double (value);
       break;
+    case PROP_FOCUS_ZONES_X:
+      self->focus_zones_x = g_value_get_int (value);
+      break;
+    case PROP_FOCUS_ZONES_Y:
+      self->focus_zones_y = g_value_get_int (value);
+      break;
+    case PROP_FOCUS_THRESHOLD:
+      self->focus_threshold = g_value_get_uint (value);
+      break;
     default:
       if (gst_mi_colour_set_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -936,6 +1013,15 @@ element_get_property (GObject * object, guint prop_id, GValue * value,
     case PROP_NOISE_SHOT:
       g_value_set_double (value, self->noise_shot);
       break;
+    case PROP_FOCUS_ZONES_X:
+      g_value_set_int (value, self->focus_zones_x);
+      break;
+    case PROP_FOCUS_ZONES_Y:
+      g_value_set_int (value, self->focus_zones_y);
+      break;
+    case PROP_FOCUS_THRESHOLD:
+      g_value_set_uint (value, self->focus_threshold);
+      break;
     default:
       if (gst_mi_colour_get_property (self->colour, (gint) prop_id - PROP_COLOUR_FIRST, value))
         break;
@@ -957,6 +1043,7 @@ element_finalize (GObject * object)
   self->act.devices = NULL;
   g_free (self->failure_note);
   self->failure_note = NULL;
+  g_queue_clear_full (&self->focus_notes, (GDestroyNotify) gst_structure_free);
   g_free (self->shading_file);
   g_free (self->act.shading_file);
   self->shading_file = self->act.shading_file = NULL;
@@ -1109,6 +1196,7 @@ element_set_caps (GstBaseTransform * base, GstCaps * incaps, GstCaps * outcaps)
 
   gst_structure_get_int (s, "width", &self->width);
   gst_structure_get_int (s, "height", &self->height);
+  self->focus_frame = 0;        /* `mibayer-focus` counts the frames collected since the caps were set */
   /* The reference's templates say [1, MAX] for both and its set_caps takes
    * anything, but its frame loop is only well defined for even widths >= 4 and
    * heights >= 3 (it leaves the last column of an odd width unwritten and reads
@@ -1529,6 +1617,9 @@ element_start (GstBaseTransform * base)
   self->act.denoise = self->denoise;
   self->act.noise_read = self->noise_read;
   self->act.noise_shot = self->noise_shot;
+  self->act.focus_zones_x = self->focus_zones_x;
+  self->act.focus_zones_y = self->focus_zones_y;
+  self->act.focus_threshold = self->focus_threshold;
   gst_mi_colour_props_copy (self->act.colour, self->colour);
   GST_OBJECT_UNLOCK (self);
   g_atomic_int_set (&self->flushing, 0);
@@ -1668,6 +1759,27 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             "the depth of the mosaic", 0.0, 65535.0, 0.0,
             G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
             G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_FOCUS_ZONES_X,
+        g_param_spec_int ("focus-zones-x", "Focus zones per row",
+            "Focus statistics of every frame, measured on the mosaic the demosaic "
+            "reads and posted as an element message `mibayer-focus` (frame, zones-x, "
+            "zones-y, threshold, score, zone-scores): zones per row; on when this "
+            "and focus-zones-y are above 0, at most half the width", 0, 64, 0,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_FOCUS_ZONES_Y,
+        g_param_spec_int ("focus-zones-y", "Focus zones per column",
+            "Focus statistics: zones per column, at most half the height; 0 = off",
+            0, 64, 0,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
+    g_object_class_install_property (object_class, PROP_FOCUS_THRESHOLD,
+        g_param_spec_uint ("focus-threshold", "Focus coring threshold",
+            "Focus statistics: a same-colour second difference counts when its "
+            "magnitude reaches this, at the depth of the mosaic (0 .. twice the "
+            "largest sample)", 0, G_MAXUINT, 0,
+            G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
+            G_PARAM_STATIC_STRINGS));
   }
 
   transform_class->transform_caps = GST_DEBUG_FUNCPTR (element_transform_caps);
@@ -1721,4 +1833,7 @@ gst_mi_bayer_element_instance_setup (GstMiBayerElement * self)
   g_queue_init (&self->pending);
   g_queue_init (&self->ready);
   g_queue_init (&self->quarantine);
+  g_queue_init (&self->focus_notes);
+  self->focus_on = FALSE;
+  self->focus_frame = 0;
 }

@@ -65,6 +65,8 @@ struct _GstMiBayerElement
   gint dpc_hot, dpc_cold;       /* defective pixel correction thresholds (bayer2rgb only); -1 = off */
   gchar *defect_file;           /* list of known defects (bayer2rgb only); NULL or "" = none */
   gdouble denoise, noise_read, noise_shot;      /* noise reduction (bayer2rgb only); denoise 0 = off */
+  gint focus_zones_x, focus_zones_y;            /* focus statistics (bayer2rgb only); on when both are > 0 */
+  guint focus_threshold;
   /* ... and latched into these by start(): the streaming thread only ever reads
    * the latched copies, so a property changed while PLAYING takes effect at the
    * next READY -> PAUSED and never races with the data flow */
@@ -82,6 +84,8 @@ struct _GstMiBayerElement
     gint dpc_hot, dpc_cold;
     gchar *defect_file;
     gdouble denoise, noise_read, noise_shot;
+    gint focus_zones_x, focus_zones_y;
+    guint focus_threshold;
   } act;
 
   /* GPU side: one shard (mibayer_ctx) per device behind a round-robin pool;
@@ -93,6 +97,10 @@ struct _GstMiBayerElement
   gdouble awb_gain[2];          /* ... and these are the red and blue gain in use (GstMiAwb, gstmicolour.h) */
   gboolean ae_on;               /* exposure=auto: the pool hands back the whole-frame histogram of every frame ... */
   gdouble ae_e;                 /* ... and this is the factor on the gains in use (GstMiAe, gstmicolour.h) */
+  gboolean focus_on;            /* focus-zones-x/-y: the pool hands back the focus zones of every frame ... */
+  guint64 focus_frame;          /* ... collected since the caps were set: the `frame` of the next message */
+  GQueue focus_notes;           /* GstStructure*: `mibayer-focus` of the frames collected, posted once flow_lock is
+                                   released (element_post_notes) */
   GQueue pending;               /* PendingFrame*, oldest first */
   GQueue ready;                 /* GstBuffer*: finished outputs collected early (the pool shrank), oldest first */
   GQueue quarantine;            /* PendingFrame*: frames lost on a GPU that ran into the wait deadline; both buffers

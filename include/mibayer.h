@@ -78,6 +78,7 @@ extern "C" {
  * with the correction off converts what it converted. */
 /* 5, later additive: noise reduction -- struct mibayer_nr and the entry points of group `nr`; a context with the curve
  * off converts what it converted. */
+/* 5, later additive: mosaic focus statistics -- struct mibayer_focus_zone and the entry points of group `focus`. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -112,6 +113,10 @@ extern "C" {
  *     mibayer_variant_count mibayer_variant_name mibayer_auto_variant mibayer_frame_class_variant
  *     mibayer_known_width_plan mibayer_ctx_variant_name mibayer_plan_selectors mibayer_launch_geometry
  *     mibayer_block_to_tile
+ * group focus: the third measurement of the ISP statistics block -- per-zone sums and counts of the same-site second
+ *   differences of the mosaic (sharpness), and the score that auto focus reads
+ *     mibayer_focus_device mibayer_set_focus mibayer_frame_focus mibayer_pool_set_focus mibayer_pool_frame_focus
+ *     mibayer_focus_score
  * group nr: noise reduction -- a sigma filter over the 24 same-site neighbours of every sample of the mosaic, its
  *   threshold a curve over the sample's level, behind the defect pass and before everything else reads the mosaic
  *     mibayer_set_nr mibayer_get_nr mibayer_nr_device mibayer_pool_set_nr mibayer_nr_curve
@@ -469,6 +474,63 @@ int mibayer_hist_percentile (const mibayer_hist *hist, int pattern, int colour, 
  * fraction, depth outside {8, 10, 12, 14, 16}, target outside (0, 1] or max_gain outside [1, 15.99]. */
 int mibayer_hist_exposure (const mibayer_hist *hist, int pattern, int depth, const double black[3],
     const double gains[3], double fraction, double target, double max_gain, double *exposure);
+
+/* ---- mosaic focus statistics (additive within version 5: a struct and the entry points of group `focus`) -------- */
+
+/* The third measurement of a camera loop, next to the zones (white balance) and the histogram (exposure): a sharpness
+ * measure per zone and CFA site of the MOSAIC, by a read-only kernel -- what auto focus, focus peaking and a lens set-up
+ * read.  Sample S(x, y), depth, max = 2^depth - 1, site s = 2 (y & 1) + (x & 1), masking and byte order exactly as in
+ * group `stats`, and so is the zone grid: zones_x x zones_y, each 1 .. 64, zones_x <= W/2, zones_y <= H/2, cells of
+ * cw = 2 ceil ((W/2) / zones_x) by ch = 2 ceil ((H/2) / zones_y).  A sample belongs to the zone of its OWN (x, y) -- its
+ * neighbours may lie in the adjacent zone --, the last row of an odd height has a zone, trailing zones may be empty and
+ * are then all zero.
+ *   responses  same-site second differences: rh = 2 S(x, y) - S(x - 2, y) - S(x + 2, y), defined only for 2 <= x <= W - 3,
+ *              and rv = 2 S(x, y) - S(x, y - 2) - S(x, y + 2), defined only for 2 <= y <= H - 3.  Nothing is reflected or
+ *              substituted: a response whose neighbour is off the frame does not exist (W = 4 has no rh, H = 3 or 4 no
+ *              rv: the zones are then zero in that direction, which is no error).  Columns >= W, stride padding and the
+ *              bits above `bits` never count.
+ *   coring     a defined response contributes when |r| >= thr, thr in 0 .. 2 max (anything else: MIBAYER_ERR_ARG); with
+ *              thr = 0 every defined response contributes, zeros included.
+ * Integers only: the result does not depend on the order of the kernel's atomic additions.  Over a flat field of
+ * independent noise of standard deviation sigma the mean response is sigma sqrt (12 / pi). */
+typedef struct mibayer_focus_zone {     /* 96 bytes */
+  uint64_t h[4];                /* sum of |rh| over the contributing samples of site s in the zone */
+  uint64_t v[4];                /* likewise |rv| */
+  uint32_t nh[4];               /* number of contributing rh */
+  uint32_t nv[4];               /* number of contributing rv */
+} mibayer_focus_zone;
+
+/* Device path: zeroes d_focus (nframes * zones_y * zones_x zones, frame-major, then row-major) on `hip_stream`, then ONE
+ * launch over the batch, frame f read at d_src + f * src_frame_bytes as by mibayer_process_device.  Valid on every
+ * bayer2rgb context (8-bit, deep, MHC, COLOUR, 24-bit, planar).  Errors as mibayer_stats_device: MIBAYER_ERR_ARG on an
+ * RGB2BAYER context, a grid outside the rule, thr > 2 max, d_src not a multiple of 4 or d_focus not a multiple of 8;
+ * MIBAYER_ERR_GEOMETRY for a frame pitch as in mibayer_process_device.  Covered by mibayer_sync when launched on the
+ * context's stream. */
+int mibayer_focus_device (mibayer_ctx *ctx, const void *d_src, size_t src_frame_bytes, int nframes, int zones_x,
+    int zones_y, uint32_t thr, mibayer_focus_zone *d_focus, void *hip_stream);
+/* Host path, as mibayer_set_stats / mibayer_frame_stats in every respect: every frame accepted after this returns also
+ * gets its focus zones, computed ONCE on the slot's device mosaic -- the one the demosaic reads, behind the defect, noise
+ * reduction and shading passes; behind the last band of a banded frame -- and downloaded behind the frame into the slot's
+ * pinned statistics buffer (zones, histogram, focus zones).  (0, 0) switches the measurement off again (the default:
+ * nothing new is then called or allocated).  Converted bytes, zones and histograms are the same with and without; a
+ * MIBAYER_FLAG_HIPGRAPH context launches without graphs meanwhile.  mibayer_frame_focus: the zones of the frame handed
+ * back last; MIBAYER_ERR_EMPTY before the first frame or when that frame was accepted with focus off, MIBAYER_ERR_ARG
+ * when nzones is not its zone count. */
+int mibayer_set_focus (mibayer_ctx *ctx, int zones_x, int zones_y, uint32_t thr);
+int mibayer_frame_focus (mibayer_ctx *ctx, mibayer_focus_zone *out, int nzones);
+/* ... of a pool: grid, threshold and zones are kept with each frame like the zones and the histogram; a frame redone on
+ * another shard brings its own, a frame returned as lost has none (MIBAYER_ERR_EMPTY). */
+int mibayer_pool_set_focus (mibayer_pool *pool, int zones_x, int zones_y, uint32_t thr);
+int mibayer_pool_frame_focus (mibayer_pool *pool, mibayer_focus_zone *out, int nzones);
+/* Focus score from zones (pure host code, doubles, in exactly this order, no fused multiply-add).  colour 0 / 1 / 2 =
+ * R / G / B (both green sites pooled), 3 = all four sites; weights NULL = 1, or nzones doubles, each finite and >= 0.
+ * Per zone z over the sites s of the colour: A_z = (double) (sum_s h[s] + sum_s v[s]), N_z = (double) (sum_s nh[s] +
+ * sum_s nv[s]), the site sums taken in uint64 first; A = sum_z w_z A_z, N = sum_z w_z N_z in zone order.  N not > 0:
+ * *score = 0, returns 0.  Else *score = A / N -- the mean absolute response at native depth --, returns 1.
+ * MIBAYER_ERR_ARG for a NULL zones or score, nzones < 1, a pattern that is no mibayer_pattern, a colour outside 0 .. 3
+ * or a weight that is negative or not finite. */
+int mibayer_focus_score (const mibayer_focus_zone *zones, int nzones, int pattern, int colour, const double *weights,
+    double *score);
 
 /* ---- lens shading correction (additive within version 5: a struct and the entry points of group `shading`) ------ */
 

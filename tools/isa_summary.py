@@ -51,6 +51,8 @@ PRODUCTION = tile_kernels() + [
     ("fused colour stage: either demosaic, every sample / channel width (run-time branches)", "bayer2rgb_colour_kernel"),
     ("mosaic zone statistics: both sample widths and byte orders (run-time branches)", "mosaic_stats_kernel"),
     ("mosaic histogram: both sample widths and byte orders (run-time branches)", "mosaic_hist_kernel"),
+    ("mosaic focus statistics: 8-bit mosaic (packed 16-bit halves)", "mosaic_focus_kernelILb1EE"),
+    ("mosaic focus statistics: 16-bit words, both byte orders", "mosaic_focus_kernelILb0EE"),
 ]
 INTERESTING = ["v_lerp_u8", "v_perm_b32", "v_alignbit_b32", "v_bfi_b32", "v_mov_b32_dpp", "ds_bpermute_b32",
                "global_load_dwordx4", "global_load_dwordx2", "global_load_dword", "global_store_dwordx4",
