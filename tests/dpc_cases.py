@@ -8,6 +8,7 @@ bits.  A workgroup walks a segment of rows: as many as 64, cut down to 16 until 
 takes the samples two columns away from the dwords left and right of its own, the first and the last dword of a row from
 the other side, and the rows two above and below from a window that is mirrored at the frame's top and bottom."""
 import collections
+import functools
 
 import numpy as np
 
@@ -78,16 +79,21 @@ def seam_rows(w, h, bits, nframes=1, cuts=()):
     return sorted(r for r in rows if 0 <= r < h)
 
 
+@functools.lru_cache(maxsize=None)
+def _planted(w, h, bits, nframes, cuts):
+    return np.array([(x, y) for y in seam_rows(w, h, bits, nframes, cuts) for x in seam_columns(w, bits)], np.uint32)
+
+
 def planted(w, h, bits, nframes=1, cuts=()):
     """(n, 2) of (x, y): a defect at every crossing of a seam column and a seam row"""
-    return np.array([(x, y) for y in seam_rows(w, h, bits, nframes, cuts) for x in seam_columns(w, bits)], np.uint32)
+    return _planted(w, h, bits, nframes, tuple(cuts)).copy()
 
 
 def plant(S, where, vmax):
     """S with the samples at `where` stuck at 0 or vmax in turn"""
     S = np.array(S, np.int64)
-    for k, (x, y) in enumerate(where):
-        S[y, x] = vmax if k % 2 == 0 else 0
+    where = np.asarray(where, np.int64).reshape(-1, 2)
+    S[where[:, 1], where[:, 0]] = np.where(np.arange(len(where)) % 2 == 0, vmax, 0)
     return S
 
 
@@ -98,18 +104,59 @@ def phase_of(where):
     return 2 * ((where[:, 1] >> 1) & 1) + ((where[:, 0] >> 1) & 1)
 
 
+def texture(case, f=0):
+    """what makes the replacement of a planted sample depend on the rows two above and below it: same-site columns
+    0, 1, 2 steps of max / 32 up in turn (the gradient of H is one or two steps), rows a sawtooth of period 8 (the
+    gradient of V is 4 max / 255 everywhere: under H's and not 0), so that V or a diagonal wins and R is the mean of two
+    rows that a window cut off at a segment seam does not have.  Both move with the frame"""
+    vmax = (1 << (case.bits or 8)) - 1
+    y, x = np.mgrid[0:case.h, 0:case.w]
+    return (vmax // 32) * (((x >> 1) + f) % 3) + (vmax // 255) * ((y + f) % 8)
+
+
 def seam_samples(case, f=0, phase=None):
-    """frame f of a case: a gentle ramp with per-site offsets (same-site steps far under max / 8) and stuck samples
-    planted on both sides of every lane, wave, strip and segment seam and on the first and last two rows and columns:
-    all of them (phase None; neighbours then hide each other from the detection), or those of one phase_of"""
+    """frame f of a case: a gentle ramp with per-site offsets and the texture above (same-site steps under max / 8) and
+    stuck samples planted on both sides of every lane, wave, strip and segment seam and on the first and last two rows
+    and columns: all of them (phase None; neighbours then hide each other from the detection), or those of one phase_of"""
     vmax = (1 << (case.bits or 8)) - 1
     where = planted(case.w, case.h, case.bits, case.nframes)
     if phase is not None:
         where = where[phase_of(where) == phase]
     y, x = np.mgrid[0:case.h, 0:case.w]
     S = vmax // 4 + (x + 2 * y + 5 * f) * (vmax // 3) // (case.w + 2 * case.h + 5 * case.nframes) \
-        + (vmax // 16) * (2 * (y & 1) + (x & 1))
+        + (vmax // 16) * (2 * (y & 1) + (x & 1)) + texture(case, f)
     return plant(S, np.roll(where, f, axis=0), vmax)
+
+
+def segment_of(case, row):
+    """(ya, yb) of the workgroups that walk `row`, for a failure message"""
+    return next(s for s in segments(case.w, case.h, case.bits, case.nframes) if s[0] <= row < s[1])
+
+
+def segment_blind(S, segs, hot, cold):
+    """dpc_model.correct as a kernel would compute it whose window stops at its segment: every segment's rows corrected
+    as a frame of their own, the rows off its ends mirrored back into it (and, in a segment of fewer than three rows,
+    held at its end)"""
+    import dpc_model as dm
+    S = np.asarray(S, np.int64)
+    out = S.copy()
+    for ya, yb in segs:
+        n = yb - ya
+        t = np.arange(-2, n + 2)
+        t = np.clip(np.where(t < 0, t + 4, np.where(t >= n, t - 4, t)), 0, n - 1)
+        out[ya:yb] = dm.correct(S[ya + t], hot, cold)[2:n + 2]
+    return out
+
+
+def long_list(case, rng, n=300):
+    """a defect list for a long case: every planted seam position and random other ones, more than 256 and fewer than
+    512 after the library has sorted it -- two workgroups of the list kernel per frame, the second partial"""
+    where = planted(case.w, case.h, case.bits, case.nframes)
+    n = max(min(n, case.w * case.h - 4), len(where))
+    rest = sorted({(x, y) for y in range(case.h) for x in range(case.w)} - {tuple(p) for p in where.tolist()})
+    more = rng.permutation(len(rest))[:n - len(where)]
+    lst = np.concatenate([where, np.asarray(rest, np.uint32).reshape(-1, 2)[more]])
+    return lst[rng.permutation(len(lst))]
 
 
 def reaches(case):
@@ -127,6 +174,21 @@ def reaches(case):
 CASES = [Case(4, 4, 0, False, 1), Case(6, 5, 0, False, 1), Case(1030, 37, 0, False, 1), Case(1032, 33, 0, False, 1),
          Case(258, 16, 0, False, 3), Case(4, 4, 12, False, 1), Case(6, 5, 16, True, 1), Case(518, 37, 12, False, 1),
          Case(518, 37, 10, True, 1), Case(130, 35, 14, False, 3)]
+
+
+# long batches of narrow frames: the launches whose workgroups walk more than MIN_ROWS rows (what each reaches:
+# tests/test_dpc_cases.py).  17 with odd seams, a last segment of one row and a half-dword tail; 17 five times; 26 twice,
+# no short segment; 25; 43; 64 as the rule gives it, one segment; 64 clamped from 65 with a short last segment; 64 clamped,
+# three segments; and 17 across a wave seam with a tail, the one wide case
+LONG_CASES = [Case(10, 35, 0, False, 512), Case(6, 70, 0, False, 256), Case(10, 52, 0, False, 512),
+              Case(8, 33, 16, True, 800), Case(10, 45, 0, False, 1000), Case(10, 64, 0, False, 1024),
+              Case(6, 67, 12, False, 1000), Case(14, 131, 0, False, 512), Case(262, 35, 0, False, 512)]
+WIDE_LONG_CASE = LONG_CASES[-1]
+
+
+def unclamped_rows(case):
+    """what the rule gives before it is clamped to MIN_ROWS .. MAX_ROWS"""
+    return case.h * strips(case.w, case.bits) * case.nframes // SPREAD
 
 
 def case_id(c):

@@ -156,5 +156,37 @@ CASES = [Case(6, 5, 0, False, 1), Case(6, 6, 0, False, 1), Case(8, 5, 0, False, 
          Case(70, 19, 16, True, 2)]
 
 
+# long batches of narrow frames: the launches whose workgroups walk more than MIN_ROWS rows, the shapes of
+# tests/dpc_cases.py (what each reaches: tests/test_nr_cases.py)
+LONG_CASES = [Case(10, 35, 0, False, 512), Case(6, 70, 0, False, 256), Case(10, 52, 0, False, 512),
+              Case(8, 33, 16, True, 800), Case(10, 45, 0, False, 1000), Case(10, 64, 0, False, 1024),
+              Case(6, 67, 12, False, 1000), Case(14, 131, 0, False, 512), Case(262, 35, 0, False, 512)]
+WIDE_LONG_CASE = LONG_CASES[-1]
+
+
+def unclamped_rows(case):
+    """what the rule gives before it is clamped to MIN_ROWS .. MAX_ROWS"""
+    return case.h * strips(case.w, case.bits) * case.nframes // SPREAD
+
+
+def segment_of(case, row):
+    """(ya, yb) of the workgroups that walk `row`, for a failure message"""
+    return next(s for s in segments(case.w, case.h, case.bits, case.nframes) if s[0] <= row < s[1])
+
+
+def segment_blind(S, segs, curve, d):
+    """nr_model.denoise as a kernel would compute it whose window stops at its segment: every segment's rows denoised as
+    a frame of their own, the rows off its ends reflected back into it (and, in a segment of fewer than five rows, held
+    at its end)"""
+    S = np.asarray(S, np.int64)
+    out = S.copy()
+    for ya, yb in segs:
+        n = yb - ya
+        t = np.arange(-REACH, n + REACH)
+        t = np.clip(np.where(t < 0, -t, np.where(t >= n, 2 * (n - 1) - t, t)), 0, n - 1)
+        out[ya:yb] = nm.denoise(S[ya + t], curve, d)[REACH:n + REACH]
+    return out
+
+
 def case_id(c):
     return "%dx%d_%s%s_x%d" % (c.w, c.h, c.bits or 8, "be" if c.sbe else "", c.nframes)

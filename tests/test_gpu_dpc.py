@@ -46,8 +46,9 @@ def run_device(ctx, frames, src_pitch=None, dst_pitch=None, offset=0):
     return np.stack([out[offset + f * dp:offset + f * dp + nb] for f in range(n)])
 
 
-def check(pkg, ctx, frames, hot, cold, defects=None, bits=0, sbe=False, where="", **kw):
-    """one call against the model; returns the share of samples the detection flags in frame 0"""
+def check(pkg, ctx, frames, hot, cold, defects=None, bits=0, sbe=False, where="", segment_of=None, **kw):
+    """one call against the model; returns the share of samples the detection flags in frame 0.  `segment_of`: row ->
+    (ya, yb) of the workgroups that walk it, for the message"""
     w, h, stride = ctx.width, ctx.height, ctx.src_stride
     ctx.set_dpc(pkg.Dpc(hot, cold, defects))
     got = run_device(ctx, frames, **kw)
@@ -56,8 +57,9 @@ def check(pkg, ctx, frames, hot, cold, defects=None, bits=0, sbe=False, where=""
         want = dm.correct_raw(frames[f], poison, w, h, stride, bits, sbe, hot, cold, defects)
         if not np.array_equal(got[f], want):
             bad = np.argwhere(got[f].reshape(h, stride) != want.reshape(h, stride))
-            raise AssertionError("%s %dx%d hot %d cold %d frame %d: %d bytes differ, first at row %d byte %d (got %d, want %d)"
-                                 % (where, w, h, hot, cold, f, len(bad), bad[0][0], bad[0][1],
+            seg = " in the segment of rows %d .. %d" % segment_of(bad[0][0]) if segment_of else ""
+            raise AssertionError("%s %dx%d hot %d cold %d frame %d: %d bytes differ, first at row %d byte %d%s (got %d, want %d)"
+                                 % (where, w, h, hot, cold, f, len(bad), bad[0][0], bad[0][1], seg,
                                     got[f].reshape(h, stride)[tuple(bad[0])], want.reshape(h, stride)[tuple(bad[0])]))
     return float(dm.flagged(sm.samples(frames[0], w, h, stride, bits, sbe), hot, cold).mean())
 
@@ -93,6 +95,28 @@ def test_defects_on_every_seam(gpu_pkg, case):
             assert share > 0
         check(gpu_pkg, ctx, frames, -1, -1, where, **kw)
         check(gpu_pkg, ctx, frames, vmax // 8, vmax // 8, where[::3], **kw)
+
+
+@pytest.mark.parametrize("planted", ["phase0", "phase1", "phase2", "phase3", "listed"])
+@pytest.mark.parametrize("case", dc.LONG_CASES, ids=dc.case_id)
+def test_segments_longer_than_the_minimum(gpu_pkg, case, planted):
+    """long batches of narrow frames, whose workgroups walk 17 .. 64 rows (tests/test_dpc_cases.py: which, and that the
+    frames show a window that stops at its segment): ONE call for the whole batch, every frame compared.  Detected by
+    threshold, one phase of the planted samples per test, so every one of them at the new seams must be found; and all
+    of them at once with a list of 257 .. 511 entries that holds every planted position: two workgroups of the list kernel
+    per frame, the second partial, up to the last frame.  Frame pitches and base pointers as in the batch test below"""
+    rng = np.random.default_rng([7, case.w, case.h, case.bits])
+    vmax = (1 << (case.bits or 8)) - 1
+    with open_case(gpu_pkg, case, pad=4) as ctx:
+        kw = dict(bits=case.bits, sbe=case.sbe, where=dc.case_id(case), segment_of=lambda row: dc.segment_of(case, row),
+                  src_pitch=ctx.src_bytes + 20, dst_pitch=ctx.src_bytes + 52, offset=4)
+        if planted == "listed":
+            lst = dc.long_list(case, rng)
+            assert 256 < len(dm.sort_defects(lst)) < 512
+            check(gpu_pkg, ctx, seam_frames(rng, case, ctx.src_stride), vmax // 8, vmax // 8, lst, **kw)
+        else:
+            frames = seam_frames(rng, case, ctx.src_stride, int(planted[-1]))
+            assert check(gpu_pkg, ctx, frames, vmax // 8, vmax // 8, None, **kw) > 0
 
 
 @pytest.mark.parametrize("bits,sbe", [(0, False)] + [(b, e) for b in (10, 12, 14, 16) for e in (False, True)],

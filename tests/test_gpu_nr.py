@@ -46,19 +46,22 @@ def run_device(ctx, frames, src_pitch=None, dst_pitch=None, offset=0):
     return np.stack([out[offset + f * dp:offset + f * dp + nb] for f in range(n)])
 
 
-def check(pkg, ctx, frames, curve, bits=0, sbe=False, where="", **kw):
-    """one call against the model: the frames' samples denoised, the stride padding still the destination's poison"""
+def check(pkg, ctx, frames, curve, bits=0, sbe=False, where="", segment_of=None, **kw):
+    """one call against the model: the frames' samples denoised, the stride padding still the destination's poison.
+    `segment_of`: row -> (ya, yb) of the workgroups that walk it, for the message"""
     w, h, stride = ctx.width, ctx.height, ctx.src_stride
     ctx.set_nr(pkg.Nr(curve))
     assert ctx.get_nr() == [int(v) for v in curve]
     got = run_device(ctx, frames, **kw)
     poison = np.full(ctx.src_bytes, DST_FILL, np.uint8)
     for f in range(len(frames)):
-        want = nm.denoise_raw(frames[f], poison, w, h, stride, bits, sbe, curve)
+        if f == 0 or not np.array_equal(frames[f], frames[f - 1]):      # (a batch of one frame repeated: one model run)
+            want = nm.denoise_raw(frames[f], poison, w, h, stride, bits, sbe, curve)
         if not np.array_equal(got[f], want):
             bad = np.argwhere(got[f].reshape(h, stride) != want.reshape(h, stride))
-            raise AssertionError("%s %dx%d frame %d: %d bytes differ, first at row %d byte %d (got %d, want %d)"
-                                 % (where, w, h, f, len(bad), bad[0][0], bad[0][1],
+            seg = " in the segment of rows %d .. %d" % segment_of(bad[0][0]) if segment_of else ""
+            raise AssertionError("%s %dx%d frame %d: %d bytes differ, first at row %d byte %d%s (got %d, want %d)"
+                                 % (where, w, h, f, len(bad), bad[0][0], bad[0][1], seg,
                                     got[f].reshape(h, stride)[tuple(bad[0])], want.reshape(h, stride)[tuple(bad[0])]))
     return got
 
@@ -93,6 +96,37 @@ def test_noisy_ramps_on_every_seam(gpu_pkg, case):
             for at_max in (False, True):
                 S, _ = nc.boundary_samples(case, at_max)
                 check(gpu_pkg, ctx, np.stack([as_bytes(rng, S, case, ctx.src_stride)] * case.nframes), curve, **kw)
+
+
+# every long case under its noisy ramps; the planted boundaries where a frame admits them; uniform random samples under
+# a rising curve for one case per width of a sample (8-bit, 16-bit big-endian)
+LONG_RUNS = [(c, "noise") for c in nc.LONG_CASES] \
+    + [(c, at) for c in nc.LONG_CASES if c.w >= 10 and c.h >= 7 for at in ("at_0", "at_max")] \
+    + [(c, "rising") for c in (nc.LONG_CASES[0], nc.LONG_CASES[3])]
+
+
+@pytest.mark.parametrize("case,content", LONG_RUNS, ids=lambda v: v if isinstance(v, str) else nc.case_id(v))
+def test_segments_longer_than_the_minimum(gpu_pkg, case, content):
+    """long batches of narrow frames, whose workgroups walk 17 .. 64 rows (tests/test_nr_cases.py: which, and that the
+    frames show a window that stops at its segment): ONE call for the whole batch and every frame compared.  The noisy
+    ramps, every frame its own noise; the planted boundaries at 0 and at max in every frame; uniform random samples under
+    a rising curve.  Frame pitches and base pointers as in the batches above"""
+    rng = np.random.default_rng([4, case.w, case.h, case.bits])
+    curve = nc.curve_of(case)
+    with open_case(gpu_pkg, case, pad=4) as ctx:
+        if content == "noise":
+            frames = np.stack([as_bytes(rng, nc.seam_samples(case, f), case, ctx.src_stride) for f in range(case.nframes)])
+        elif content == "rising":
+            tm = nm.t_max(nc.depth(case))
+            curve = [tm * i // 16 for i in range(17)]
+            frames = np.stack([sc.random_frame(rng, case.w, case.h, case.bits, ctx.src_stride, case.sbe).reshape(-1)
+                               for _ in range(case.nframes)])
+        else:
+            S, _ = nc.boundary_samples(case, content == "at_max")
+            frames = np.stack([as_bytes(rng, S, case, ctx.src_stride)] * case.nframes)
+        check(gpu_pkg, ctx, frames, curve, bits=case.bits, sbe=case.sbe, where=nc.case_id(case) + " " + content,
+              segment_of=lambda row: nc.segment_of(case, row), src_pitch=ctx.src_bytes + 20,
+              dst_pitch=ctx.src_bytes + 36, offset=4)
 
 
 @pytest.mark.parametrize("bits,sbe", [(0, False)] + [(b, e) for b in (10, 12, 14, 16) for e in (False, True)],

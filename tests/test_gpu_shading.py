@@ -3,14 +3,16 @@ mibayer_shade_device and through the host path, bit-exact against tests/shading_
 
 The kernel (csrc/mibayer_kernels.hip): a lane owns one dword of a row -- 4 samples of an 8-bit mosaic, 2 of a deep one; a
 wave spans 64 dwords, a workgroup 256 = one strip; a row whose width is 2 mod 4 ends in a half dword that is stored as 16
-bits.  A workgroup walks kShadeMinRows = 16 rows of a small launch, cell row by cell row, kShadeAhead = 8 rows at a time,
-and reads a new row of nodes at every cell-row seam.  Widths: one lane (4), a tail only behind it (6), past a wave (258),
+bits.  A workgroup walks kShadeMinRows = 16 rows of a small launch and up to kShadeMaxRows = 64 of a large one
+(tests/shading_cases.py restates the rule; section E runs the long ones), cell row by cell row, kShadeAhead = 8 rows at a
+time, and reads a new row of nodes at every cell-row seam.  Widths: one lane (4), a tail only behind it (6), past a wave (258),
 past a strip with a tail (1030; 518 for 16-bit samples).  Heights: the smallest, an odd one, one past two segments (37),
 and one that ends exactly on a cell-row seam."""
 import numpy as np
 import pytest
 
 import band_cases as bc
+import shading_cases as shc
 import shading_model as shm
 import stats_model as sm
 import strip_cases as sc
@@ -32,15 +34,7 @@ def seam_height(ky):
     return max(ch, 40 // ch * ch)
 
 
-def site_planes(w, h, kx, ky, rng=None):
-    """four visibly different site planes (a swapped site or row parity shows), each a ramp in both directions"""
-    nx, ny = shm.nodes(w, h, kx, ky)
-    j, i = np.mgrid[0:ny, 0:nx]
-    t = np.stack([base + 37 * s + (90 + 20 * s) * i + (150 - 30 * s) * j for s, base in enumerate((3000, 5200, 7100, 9400))])
-    if rng is not None:
-        t = t + rng.integers(0, 64, t.shape)
-    assert t.max() <= shm.MAX_ENTRY
-    return t.astype(np.uint16)
+site_planes = shc.site_planes
 
 
 def run_device(ctx, frames, pitch=None, offset=0, in_place=False):
@@ -81,8 +75,9 @@ def run_device(ctx, frames, pitch=None, offset=0, in_place=False):
     return pick(out), pick(before)
 
 
-def check(pkg, ctx, frames, table, kx, ky, black, bits=0, sbe=False, where="", **kw):
-    """one launch in place and one out of place, each against the model"""
+def check(pkg, ctx, frames, table, kx, ky, black, bits=0, sbe=False, where="", segment_of=None, **kw):
+    """one launch in place and one out of place, each against the model.  `segment_of`: row -> (ya, yb) of the
+    workgroups that walk it, for the message"""
     w, h, stride = ctx.width, ctx.height, ctx.src_stride
     ctx.set_shading(pkg.Shading(kx, ky, table, black))
     for in_place in (False, True):
@@ -91,9 +86,11 @@ def check(pkg, ctx, frames, table, kx, ky, black, bits=0, sbe=False, where="", *
             want = shm.shade_raw(frames[f], table, kx, ky, black, w, h, stride, bits, sbe, dst=before[f])
             if not np.array_equal(got[f], want):
                 bad = np.argwhere(got[f].reshape(h, stride) != want.reshape(h, stride))
-                raise AssertionError("%s %dx%d k=(%d,%d) %s frame %d: %d bytes differ, first at row %d byte %d (got %d, want %d)"
+                seg = " in the segment of rows %d .. %d" % segment_of(bad[0][0]) if segment_of else ""
+                raise AssertionError("%s %dx%d k=(%d,%d) %s frame %d: %d bytes differ, first at row %d byte %d%s (got %d, want %d)"
                                      % (where, w, h, kx, ky, "in place" if in_place else "out of place", f, len(bad), bad[0][0],
-                                        bad[0][1], got[f].reshape(h, stride)[tuple(bad[0])], want.reshape(h, stride)[tuple(bad[0])]))
+                                        bad[0][1], seg, got[f].reshape(h, stride)[tuple(bad[0])],
+                                        want.reshape(h, stride)[tuple(bad[0])]))
 
 
 # -- A. widths, heights, grids ---------------------------------------------------------------------------------------------
@@ -379,3 +376,24 @@ def test_pool_refuses_what_a_context_refuses(gpu_pkg):
     with pkg.Pool([0, 0], w, h, "bggr", "ARGB", flags=pkg.FLAG_RGB2BAYER) as inv:
         assert L.mibayer_pool_set_shading(inv._h, pkg.Shading(4, 4, table)) == pkg.ERR_ARG
         assert L.mibayer_pool_set_shading(inv._h, None) == pkg.OK       # off is what it is already
+
+
+# -- E. segments longer than the minimum ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("case", shc.LONG_CASES, ids=shc.case_id)
+def test_segments_longer_than_the_minimum(gpu_pkg, case):
+    """long batches of narrow frames, whose workgroups walk 18 .. 64 rows and start inside a cell row
+    (tests/test_shading_cases.py: which rows and phases, and that these tables show a wrong weight or stale nodes): ONE
+    launch for the whole batch, in place and out of place, every frame random and every frame compared; four black
+    levels; frames 20 bytes further apart than they are long, the base pointer at 4 mod 16"""
+    rng = np.random.default_rng([9, case.w, case.h, case.ky])
+    vmax = (1 << (case.bits or 8)) - 1
+    stride = sc.src_row_bytes(case.w, case.bits) + 4
+    with gpu_pkg.Context(case.w, case.h, sc.ORDERS[(case.w + case.h) % 4], "RGBx", src_stride=stride, bits=case.bits,
+                         src_big_endian=case.sbe, device=0) as ctx:
+        table = site_planes(case.w, case.h, case.kx, case.ky, rng)
+        frames = np.stack([sc.random_frame(rng, case.w, case.h, case.bits, stride, case.sbe).reshape(-1)
+                           for _ in range(case.nframes)])
+        check(gpu_pkg, ctx, frames, table, case.kx, case.ky, (vmax // 16, vmax // 20, vmax // 18, vmax // 14), case.bits,
+              case.sbe, where=shc.case_id(case), segment_of=lambda row: shc.segment_of(case, row),
+              pitch=ctx.src_bytes + 20, offset=4)
