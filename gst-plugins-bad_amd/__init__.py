@@ -92,7 +92,8 @@ FLAG_DST_BIG_ENDIAN = 1 << 15
 FLAG_DST_24BIT = 1 << 21        # 3-byte pixels, RGB / BGR; dst_stride defaults to ROUND_UP_4(3 * width)
 FLAG_DST_PLANAR = 1 << 22       # three planes of dst_stride x height bytes; dst_stride defaults to ROUND_UP_4(width)
 FLAG_MHC = 1 << 16              # Malvar-He-Cutler demosaic instead of the reference's bilinear one
-METHODS = {"bilinear": 0, "mhc": FLAG_MHC}      # the `method` keyword of make_cfg / Context / Pool
+FLAG_HALF = 1 << 23             # half-size demosaic: one RGB pixel per CFA quad, output W / 2 x H >> 1
+METHODS = {"bilinear": 0, "mhc": FLAG_MHC, "half": FLAG_HALF}   # the `method` keyword of make_cfg / Context / Pool
 FLAG_COLOUR = 1 << 19           # fused colour stage: black level, Q12 matrix, tone curve (struct mibayer_colour)
 TONE_LINEAR, TONE_SRGB, TONE_GAMMA = 0, 1, 2
 
@@ -574,7 +575,8 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
              method="bilinear", colour=None):
     """bits / src_big_endian / out16 / dst_big_endian: the deep-sample flags (or pass them in `flags`); a FORMATS16
     name implies out16, a FORMATS24 name ("RGB", "BGR") FLAG_DST_24BIT, a FORMATS_PLANAR name FLAG_DST_PLANAR.
-    method: "bilinear" (the reference's, bit-exact) or "mhc" (Malvar-He-Cutler, FLAG_MHC).
+    method: "bilinear" (the reference's, bit-exact), "mhc" (Malvar-He-Cutler, FLAG_MHC) or "half" (FLAG_HALF: one pixel
+    per CFA quad; width / height stay the mosaic's).
     colour: None / False = no colour stage; True or a Colour = FLAG_COLOUR (Context / Pool apply the Colour)"""
     if colour is not None and colour is not False:
         flags |= FLAG_COLOUR
@@ -600,7 +602,8 @@ def make_cfg(width, height, pattern="bggr", fmt="RGBx", src_stride=0, dst_stride
 
 def planes(frame, width, height, dst_stride=0):
     """A converted planar frame (MIBAYER_FLAG_DST_PLANAR, 3 * dst_stride * height bytes) viewed as (3, height, width):
-    plane k, row y, the first `width` bytes of the stride.  frame: a numpy uint8 array (the host path's), or a torch
+    plane k, row y, the first `width` bytes of the stride; width / height are the OUTPUT's (a half-size context's
+    out_width / out_height).  frame: a numpy uint8 array (the host path's), or a torch
     uint8 tensor -- over device memory the context converted into through its data_ptr(), as bench.py passes tensors --
     and the result is of the same kind.  A view of the same memory: nothing is copied or computed."""
     stride = dst_stride or (width + 3) & ~3
@@ -771,11 +774,14 @@ class Context:
         self.src_stride, self.dst_stride = out.src_stride, out.dst_stride
         self.src_bytes = out.src_stride * out.height
         self.planar = bool(out.flags & FLAG_DST_PLANAR)
-        self.dst_rows = (3 if self.planar else 1) * out.height  # rows of dst_stride bytes in a frame (stacked planes)
+        self.half = bool(out.flags & FLAG_HALF)
+        # the output frame's pixels: the mosaic's, or one per CFA quad (FLAG_HALF; the last row of an odd height is dropped)
+        self.out_width, self.out_height = (out.width // 2, out.height >> 1) if self.half else (out.width, out.height)
+        self.dst_rows = (3 if self.planar else 1) * self.out_height     # rows of dst_stride bytes in a frame (stacked planes)
         self.dst_bytes = out.dst_stride * self.dst_rows
         self.variant_name = lib().mibayer_ctx_variant_name(self._h).decode()
         self.deep = bool(out.flags & (FLAG_SRC_BITS_MASK | FLAG_DST_16BIT | FLAG_DST_24BIT | FLAG_DST_PLANAR))
-        self.method = "mhc" if out.flags & FLAG_MHC else "bilinear"
+        self.method = "mhc" if out.flags & FLAG_MHC else "half" if self.half else "bilinear"
         self.colour = bool(out.flags & FLAG_COLOUR)
         self._zones = (1, 1)            # the grid frame_stats() asks for: the last one set_stats() switched on
         self._fzones = (1, 1)           # ... and frame_focus(): the last one set_focus() switched on
@@ -1232,4 +1238,4 @@ class Context:
     def planes(self, frame):
         """planes() of a frame this context converted"""
         assert self.planar
-        return planes(frame, self.width, self.height, self.dst_stride)
+        return planes(frame, self.out_width, self.out_height, self.dst_stride)

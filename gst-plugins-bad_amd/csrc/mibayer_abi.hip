@@ -363,6 +363,10 @@ struct mibayer_ctx {
    * copy of the stage under the lock when it is accepted (Slot::stage), a device-path call one per call; the copy
    * travels in the kernel arguments, so mibayer_set_colour never touches what is already queued */
   bool colour = false;
+  /* MIBAYER_FLAG_HALF: bayer2rgb_half_kernel, a deep context (8-bit ones included) whose OUTPUT is out_width x
+   * out_height = W / 2 x H >> 1; cfg.width / cfg.height stay the mosaic's.  Every other context: the cfg's */
+  bool half = false;
+  int out_width = 0, out_height = 0;
   mutable std::mutex colour_mu;
   mibayer_colour colour_user;           /* as set (mibayer_get_colour) */
   ColourStage colour_stage;             /* as the kernel takes it */
@@ -892,8 +896,8 @@ static void make_deep_plan (mibayer_ctx *c)
   c->kind.out16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
   DeepParams &q = c->deep_args;
   q = DeepParams ();
-  q.width = f.width;
-  q.height = f.height;
+  q.width = c->half ? c->out_width : f.width;         /* the half-size kernel's arguments are in output geometry */
+  q.height = c->half ? c->out_height : f.height;
   q.src_stride = f.src_stride;
   q.dst_stride = f.dst_stride;
   q.dn_last = f.height >= 4 ? f.height - 4 : 1;        /* gstbayer2rgb.c:430-447 */
@@ -904,10 +908,10 @@ static void make_deep_plan (mibayer_ctx *c)
   q.px3 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
   if (f.flags & MIBAYER_FLAG_DST_PLANAR) {
     /* the offsets are plane indices; the bilinear kernel's R' / B' are B / R for rggb / gbrg (plan_selectors) */
-    const bool swap = !(c->kind.mhc || c->colour) && (f.pattern == MIBAYER_RGGB || f.pattern == MIBAYER_GBRG);
+    const bool swap = !(c->kind.mhc || c->colour || c->half) && (f.pattern == MIBAYER_RGGB || f.pattern == MIBAYER_GBRG);
     q.planar = 0x100 | (swap ? f.b_off : f.r_off) | f.g_off << 2 | (swap ? f.r_off : f.b_off) << 4;
   }
-  if (c->kind.mhc || c->colour)
+  if (c->kind.mhc || c->colour || c->half)
     make_cgd_selectors (c, depth);
   for (int k = 0; k < 4; k++)
     q.sel[k] = c->sel[k];
@@ -964,6 +968,12 @@ static int launch_deep_kernel (const mibayer_ctx *c, DeepParams &q, int nframes,
   } else if (!stage) {
     colour_snapshot (c, &now);
     stage = &now;
+  }
+  if (c->half) {                /* launched whole: a HALF context has no host-path bands */
+    if (chunk0 != 0 || nchunks >= 0)
+      return MIBAYER_ERR_ARG;
+    HIP_TRY (launch_half (q, c->kind.in8, c->kind.out16, stage, nframes, stream));
+    return MIBAYER_OK;
   }
   HIP_TRY (launch_strip (q, c->kind, stage, nframes, stream, chunk0, nchunks));
   return MIBAYER_OK;
@@ -1369,10 +1379,14 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   constexpr uint32_t kDeepFlags = MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_SRC_BIG_ENDIAN | MIBAYER_FLAG_DST_16BIT
       | MIBAYER_FLAG_DST_BIG_ENDIAN | MIBAYER_FLAG_DST_24BIT | MIBAYER_FLAG_DST_PLANAR;
   if (f.flags & ~(uint32_t) (MIBAYER_FLAG_HIPGRAPH | MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_HIPGRAPH_CHAIN | kDeepFlags
-          | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
+          | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR | MIBAYER_FLAG_HALF))
     return MIBAYER_ERR_ARG;
-  if ((f.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR)) && ((f.flags & MIBAYER_FLAG_RGB2BAYER) || f.variant != 0))
+  if ((f.flags & (MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR | MIBAYER_FLAG_HALF))
+      && ((f.flags & MIBAYER_FLAG_RGB2BAYER) || f.variant != 0))
     return MIBAYER_ERR_ARG;                     /* one kernel shape, and no MHC mosaicking */
+  const bool half = (f.flags & MIBAYER_FLAG_HALF) != 0;
+  if (half && (f.flags & MIBAYER_FLAG_MHC))
+    return MIBAYER_ERR_ARG;                     /* a quad's own samples: nothing to interpolate */
   const uint32_t src_bits = (f.flags & MIBAYER_FLAG_SRC_BITS_MASK) >> 8;
   if ((f.flags & kDeepFlags) && (f.flags & MIBAYER_FLAG_RGB2BAYER))
     return MIBAYER_ERR_ARG;                     /* high-bit rgb2bayer does not exist */
@@ -1429,17 +1443,18 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
   const bool dst16 = (f.flags & MIBAYER_FLAG_DST_16BIT) != 0;
   const bool dst24 = (f.flags & MIBAYER_FLAG_DST_24BIT) != 0;
   const bool planar = (f.flags & MIBAYER_FLAG_DST_PLANAR) != 0;
-  if ((src_bits || dst16 || dst24 || planar) && f.width > (1 << 26))
+  if ((src_bits || dst16 || dst24 || planar || half) && f.width > (1 << 26))
     return MIBAYER_ERR_GEOMETRY;
+  const int out_w = half ? f.width / 2 : f.width, out_h = half ? f.height >> 1 : f.height;
   const int dst_px = dst16 ? 8 : dst24 ? 3 : planar ? 1 : 4;    /* bytes of a pixel in a row (of a plane) */
   if (f.src_stride == 0)
     f.src_stride = src_row;             /* GST_ROUND_UP_4, gstbayer2rgb.c:477 */
   if (f.dst_stride == 0)                /* gstbayer2rgb.c:344; 3-byte pixels: GStreamer's RGB stride, ROUND_UP_4 (3 w);
                                            planes: ROUND_UP_4 (w) */
-    f.dst_stride = (dst_px * f.width + 3) & ~3;
+    f.dst_stride = (dst_px * out_w + 3) & ~3;
   if (f.src_stride < src_row || (f.src_stride & 3))
     return MIBAYER_ERR_GEOMETRY;
-  if (f.dst_stride < dst_px * f.width || (f.dst_stride & (dst16 ? 7 : 3)))
+  if (f.dst_stride < dst_px * out_w || (f.dst_stride & (dst16 ? 7 : 3)))
     return MIBAYER_ERR_GEOMETRY;
   /* 3-byte pixels: RGB or BGR -- the bytes of RGBx / BGRx without the fourth, so the selectors are those layouts' */
   if (planar) {
@@ -1448,7 +1463,7 @@ static int validate (const mibayer_cfg *in, mibayer_cfg *out)
     if ((unsigned) f.r_off > 2u || (unsigned) f.g_off > 2u || (unsigned) f.b_off > 2u || f.r_off == f.g_off
         || f.g_off == f.b_off || f.r_off == f.b_off)
       return MIBAYER_ERR_LAYOUT;
-    if (3ull * (unsigned long long) f.dst_stride * (unsigned long long) f.height > (unsigned long long) SIZE_MAX)
+    if (3ull * (unsigned long long) f.dst_stride * (unsigned long long) out_h > (unsigned long long) SIZE_MAX)
       return MIBAYER_ERR_GEOMETRY;
   } else if (dst24 ? !(f.g_off == 1 && ((f.r_off == 0 && f.b_off == 2) || (f.r_off == 2 && f.b_off == 0)))
       : !layout_known (f.r_off, f.g_off, f.b_off))
@@ -1578,7 +1593,10 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
   c->cfg = f;
   c->device = dev;
   c->src_bytes = (size_t) f.src_stride * f.height;
-  c->dst_bytes = (size_t) f.dst_stride * f.height * ((f.flags & MIBAYER_FLAG_DST_PLANAR) ? 3 : 1);
+  c->half = (f.flags & MIBAYER_FLAG_HALF) != 0;
+  c->out_width = c->half ? f.width / 2 : f.width;
+  c->out_height = c->half ? f.height >> 1 : f.height;
+  c->dst_bytes = (size_t) f.dst_stride * c->out_height * ((f.flags & MIBAYER_FLAG_DST_PLANAR) ? 3 : 1);
   c->inverse = (f.flags & MIBAYER_FLAG_RGB2BAYER) != 0;
   c->kind.mhc = (f.flags & MIBAYER_FLAG_MHC) != 0;
   c->colour = (f.flags & MIBAYER_FLAG_COLOUR) != 0;
@@ -1586,7 +1604,7 @@ extern "C" int mibayer_create (const mibayer_cfg *cfg, mibayer_ctx **out)
     mibayer_colour_init (&c->colour_user);
     (void) colour_stage_from (&c->colour_user, &c->colour_stage);
   }
-  c->deep = c->kind.mhc || c->colour
+  c->deep = c->kind.mhc || c->colour || c->half
       || (f.flags & (MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT
               | MIBAYER_FLAG_DST_PLANAR)) != 0;
   {
@@ -1925,7 +1943,7 @@ extern "C" int mibayer_plan_selectors (const mibayer_cfg *cfg, uint32_t sel[4],
   if (rc != MIBAYER_OK)
     return rc;
   if (f.flags & (MIBAYER_FLAG_RGB2BAYER | MIBAYER_FLAG_SRC_BITS_MASK | MIBAYER_FLAG_DST_16BIT | MIBAYER_FLAG_DST_24BIT
-          | MIBAYER_FLAG_DST_PLANAR | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR))
+          | MIBAYER_FLAG_DST_PLANAR | MIBAYER_FLAG_MHC | MIBAYER_FLAG_COLOUR | MIBAYER_FLAG_HALF))
     return MIBAYER_ERR_ARG;
   plan_selectors (f, sel, *swap_rows);
   return MIBAYER_OK;
@@ -1957,6 +1975,8 @@ extern "C" int mibayer_known_width_plan (int width, int *variant, int *band)
 
 extern "C" const char *mibayer_ctx_variant_name (const mibayer_ctx *c)
 {
+  if (c && c->half)
+    return c->colour ? "colour_half_256x4" : "half_256x4";
   if (c && c->colour)
     return c->kind.mhc ? "colour_mhc_256x16" : "colour_bilinear_256x16";
   if (c && c->kind.mhc)
@@ -3210,11 +3230,12 @@ static int download_frame (mibayer_ctx *c, const Slot &s, uint8_t *dst, size_t r
   const size_t stride = (size_t) f.dst_stride;
   /* planar output: the rows of each of the three planes; the planes lie one under the other, so a whole frame is
    * one run of height x planes rows */
-  const bool whole = y0 == 0 && y1 == f.height;
+  const int height = c->out_height;     /* destination rows (of a plane) */
+  const bool whole = y0 == 0 && y1 == height;
   const int runs = whole ? 1 : dst_planes (c);
-  const size_t rows = whole ? (size_t) f.height * dst_planes (c) : (size_t) (y1 - y0);
+  const size_t rows = whole ? (size_t) height * dst_planes (c) : (size_t) (y1 - y0);
   for (int k = 0; k < runs; k++) {
-    const size_t doff = ((size_t) k * f.height + y0) * stride;
+    const size_t doff = ((size_t) k * height + y0) * stride;
     if (stride == row_bytes) {
       HIP_TRY (hipMemcpyAsync (dst + doff, s.d_dst + doff, rows * stride, hipMemcpyDeviceToHost, c->s_d2h));
     } else {
@@ -3244,7 +3265,7 @@ static int choose_host_bands (const mibayer_ctx *c)
   if (want > kMaxHostBands)
     want = kMaxHostBands;
   const size_t big_side = c->inverse ? c->src_bytes : c->dst_bytes;     /* the 4 (8) B/px frame */
-  if (want < 2 || (!c->deep && plan_for (c, 1).var->persistent)
+  if (want < 2 || c->half || (!c->deep && plan_for (c, 1).var->persistent)
       || big_side < ((size_t) 16 << 20))        /* below ~4K the extra enqueues cost more
                                                    than the overlap gains (1080p: -10 %) */
     return 1;
@@ -3428,7 +3449,7 @@ static int enqueue_plain (mibayer_ctx *c, Slot &s, const uint8_t *src,
   }
   Range r ("mibayer:d2h");
   HIP_TRY (hipStreamWaitEvent (c->s_d2h, s.ev_kernel, 0));
-  const int rc = download_frame (c, s, dst, row_bytes, 0, c->cfg.height);
+  const int rc = download_frame (c, s, dst, row_bytes, 0, c->out_height);
   if (rc != MIBAYER_OK)
     return rc;
   const int stats_rc = slot_download_stats (c, s);
@@ -3442,7 +3463,7 @@ static size_t written_row_bytes (const mibayer_ctx *c)
 {
   return c->inverse ? (size_t) ((c->cfg.width + 3) & ~3)
       : (size_t) (c->kind.out16 ? 8 : (c->cfg.flags & MIBAYER_FLAG_DST_24BIT) ? 3 : dst_planes (c) == 3 ? 1 : 4)
-      * c->cfg.width;
+      * c->out_width;
 }
 
 static int enqueue_frame (mibayer_ctx *c, const uint8_t *src, uint8_t *dst,
@@ -4674,7 +4695,7 @@ extern "C" int mibayer_fill_synthetic (mibayer_ctx *c, void *d_src,
   /* the generator writes 8-bit mosaics: an MHC, colour, 24-bit or planar context of one takes it, no other deep context
    * does */
   if (!c || !d_src || nframes < 0 || c->inverse
-      || (c->deep && !((c->kind.mhc || c->colour || c->deep_args.px3 || c->deep_args.planar) && c->kind.in8)))
+      || (c->deep && !((c->kind.mhc || c->colour || c->half || c->deep_args.px3 || c->deep_args.planar) && c->kind.in8)))
     return MIBAYER_ERR_ARG;
   if (nframes > 1 && src_frame_bytes < c->src_bytes)
     return MIBAYER_ERR_GEOMETRY;

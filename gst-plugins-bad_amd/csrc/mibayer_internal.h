@@ -306,6 +306,27 @@ struct StripKind { bool mhc, in8, out16; };
 hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage *stage, int nframes, hipStream_t stream,
     long long chunk0 = 0, long long nchunks = -1);
 
+/* Half-size demosaic (MIBAYER_FLAG_HALF, bayer2rgb_half_kernel; include/mibayer.h, group `half`): one output pixel per
+ * CFA quad, pointwise.  A lane owns 4 output pixels (8 source columns of two rows), a wave a strip of kHalfWavePixels
+ * output pixels x kHalfRows output rows, a workgroup four such waves in launch order.  One kernel: sample width, output
+ * format and the colour stage are uniform run-time branches. */
+constexpr int kHalfLanePixels = 4;
+constexpr int kHalfWavePixels = 64 * kHalfLanePixels;
+constexpr int kHalfGroupPixels = 4 * kHalfWavePixels;   /* a workgroup's four waves side by side, when the row is that long */
+constexpr int kHalfRows = 4;
+/* the kernel's argument: the strip kernels' in OUTPUT geometry (d.width = OW, d.height = OH, so that the strip stores'
+ * plane pitch and row ends are the output's; d.src_stride, d.in_sel, d.mask2, d.out_shift, d.green_odd, d.red_odd,
+ * d.vmax, d.sel_cgd[0], d.px3, d.planar as the colour kernel reads them) + the colour kernel's switches and stage */
+struct HalfParams {
+  DeepParams d;
+  int in8, out16;
+  int colour;                   /* run the stage (MIBAYER_FLAG_COLOUR) */
+  ColourStage s;
+};
+/* one launch over `nframes` frames (or the p.d.nlist frames of the list); stage = NULL: no colour stage */
+hipError_t launch_half (const DeepParams &p, bool in8, bool out16, const ColourStage *stage, int nframes,
+    hipStream_t stream);
+
 /* Mosaic zone statistics (mosaic_stats_kernel; include/mibayer.h, group `stats`): read-only over the mosaic, one kernel
  * for both sample widths and byte orders (uniform run-time branches) */
 constexpr int kStatsSegRows = 64;       /* rows a workgroup walks; even, so a segment starts on an even row */

@@ -2273,6 +2273,307 @@ hipError_t launch_strip (const DeepParams &p, StripKind kind, const ColourStage 
 }
 
 /* ------------------------------------------------------------------------- */
+/* half-size demosaic (MIBAYER_FLAG_HALF)                                      */
+/* ------------------------------------------------------------------------- */
+/* One output pixel per CFA quad (include/mibayer.h, group `half`): R and B are the quad's own samples, G the rounded
+ * mean of its two greens at native depth; then the colour stage (optional) and the deep path's output conversion and
+ * layouts.  Pointwise: no neighbourhood, no halo, no border rule, no LDS but the stage's tone table.
+ *
+ * Shape: a lane owns 4 output pixels = 8 source columns of two rows (one 8-byte load per row from an 8-bit mosaic, one
+ * 16-byte load from 16-bit words; rows need only be dword-aligned), a wave a strip of kHalfWavePixels output pixels x
+ * kHalfRows output rows.  It issues all 2 kHalfRows row loads up front, then walks down in a ROLLED loop -- the rows
+ * rotate through the registers -- so that the stage and the three store families exist once in the code (the library
+ * has a size cap).  One kernel: sample width, output format and the stage are uniform run-time branches.  A row's last
+ * lane may hold 1, 2 or 3 pixels (OW may be odd): its loads stay inside the row's samples and its stores write exactly
+ * px * n bytes -- the next row, or the next plane, may start right behind them. */
+
+struct HalfRaw { uint32_t w[4]; };      /* 8-bit mosaic: w[0], w[1] = columns 0..3, 4..7; words: w[i] = columns 2i, 2i+1 */
+
+/* the lane's samples of one mosaic row; n = its output pixels (<= 0: none).  FULL (wave-uniform: every lane of the wave
+ * has n = 4): one load, nothing masked; else dword by dword -- 2 n columns are read and not a dword more */
+template <bool FULL>
+__device__ __forceinline__ HalfRaw half_load (bool in8, const uint8_t *row, int g, int n)
+{
+  HalfRaw r = { { 0u, 0u, 0u, 0u } };
+  if (in8) {
+    const uint8_t *q = row + 8 * (size_t) g;
+    if constexpr (FULL) {
+      const u32x2_a4 c = __builtin_nontemporal_load ((const u32x2_a4 *) q);
+      r.w[0] = c.x;
+      r.w[1] = c.y;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; i++)
+        if (2 * i < n)
+          r.w[i] = *(const uint32_t *) (q + 4 * i);
+    }
+  } else {
+    const uint8_t *q = row + 16 * (size_t) g;
+    if constexpr (FULL) {
+      const u32x4_a4 c = __builtin_nontemporal_load ((const u32x4_a4 *) q);
+      r.w[0] = c.x;
+      r.w[1] = c.y;
+      r.w[2] = c.z;
+      r.w[3] = c.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (i < n)
+          r.w[i] = *(const uint32_t *) (q + 4 * i);
+    }
+  }
+  return r;
+}
+
+/* the two samples of output pixel i in one row as [left | right << 16], masked, in host byte order */
+__device__ __forceinline__ void half_pairs (const HalfParams &hp, const HalfRaw &r, uint32_t (&x)[4])
+{
+  if (hp.in8) {
+    x[0] = __builtin_amdgcn_perm (r.w[0], r.w[0], 0x0c010c00u);
+    x[1] = __builtin_amdgcn_perm (r.w[0], r.w[0], 0x0c030c02u);
+    x[2] = __builtin_amdgcn_perm (r.w[1], r.w[1], 0x0c010c00u);
+    x[3] = __builtin_amdgcn_perm (r.w[1], r.w[1], 0x0c030c02u);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      x[i] = __builtin_amdgcn_perm (r.w[i], r.w[i], hp.d.in_sel) & hp.d.mask2;
+  }
+}
+
+/* n (1 .. 4) 4-byte pixels of group g, or 3-byte ones (px3: byte 3 of every pixel dropped, as store_strip8 does) */
+__device__ __forceinline__ void half_store8 (uint8_t *out, int g, int n, bool px3, u32x4 v)
+{
+  if (n <= 0)
+    return;
+  if (px3) {
+    uint8_t *q = out + 12 * (size_t) g;
+    const uint32_t d0 = __builtin_amdgcn_perm (v.y, v.x, 0x04020100u);
+    const uint32_t d1 = __builtin_amdgcn_perm (v.z, v.y, 0x05040201u);
+    const uint32_t d2 = __builtin_amdgcn_perm (v.w, v.z, 0x06050402u);
+    if (n >= 4) {
+      const u32x3_a4 three = { d0, d1, d2 };
+      __builtin_nontemporal_store (three, (u32x3_a4 *) q);
+    } else if (n == 3) {                /* 9 bytes */
+      const u32x2_a4 two = { d0, d1 };
+      __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+      __builtin_nontemporal_store ((uint8_t) d2, q + 8);
+    } else if (n == 2) {                /* 6 bytes */
+      __builtin_nontemporal_store (d0, (uint32_t *) q);
+      __builtin_nontemporal_store ((uint16_t) d1, (uint16_t *) (q + 4));
+    } else {                            /* 3 bytes */
+      __builtin_nontemporal_store ((uint16_t) d0, (uint16_t *) q);
+      __builtin_nontemporal_store ((uint8_t) (d0 >> 16), q + 2);
+    }
+  } else {
+    uint8_t *q = out + 16 * (size_t) g;
+    if (n >= 4) {
+      __builtin_nontemporal_store (v, (u32x4_a4 *) q);
+    } else {
+      if (n >= 2) {
+        const u32x2_a4 two = { v.x, v.y };
+        __builtin_nontemporal_store (two, (u32x2_a4 *) q);
+      }
+      if (n & 1)
+        __builtin_nontemporal_store (n == 1 ? v.x : v.z, (uint32_t *) (q + 4 * (n - 1)));
+    }
+  }
+}
+
+/* n (1 .. 4) samples of one plane's row: a dword, or a 16-bit and / or a byte store */
+__device__ __forceinline__ void half_plane (global_u8 *q, int n, uint32_t a)
+{
+  if (n >= 4) {
+    __builtin_nontemporal_store (a, (global_u32 *) q);
+  } else {
+    if (n >= 2)
+      __builtin_nontemporal_store ((uint16_t) a, (global_u16 *) q);
+    if (n & 1)
+      __builtin_nontemporal_store ((uint8_t) (a >> (8 * (n - 1))), q + (n - 1));
+  }
+}
+
+/* 8-byte pixels: store_strip16's quad exchange (every lane of the wave calls this), with pieces of one pixel where an
+ * odd row ends */
+__device__ __forceinline__ void half_store16 (const DeepParams &p, uint8_t *out, int g, int lane, u32x4 v0, u32x4 v1)
+{
+  const int k = lane & 3;
+  u32x4 s0, s1;
+  deep_quad_pieces (v0, v1, k, s0, s1);
+  const int qg = g - k;                                 /* first group of the quad */
+  uint8_t *q = out + 32 * (size_t) qg + 16 * k;
+  /* pixels of the row from this lane's piece of the quad's first / last 64 bytes on */
+  const int ma = p.width - (4 * (qg + (k >> 1)) + 2 * (k & 1)), mb = ma - 8;
+  if (ma >= 2) {
+    *(u32x4_a4 *) q = s0;
+  } else if (ma == 1) {
+    const u32x2_a4 one = { s0.x, s0.y };
+    *(u32x2_a4 *) q = one;
+  }
+  if (mb >= 2) {
+    *(u32x4_a4 *) (q + 64) = s1;
+  } else if (mb == 1) {
+    const u32x2_a4 one = { s1.x, s1.y };
+    *(u32x2_a4 *) (q + 64) = one;
+  }
+}
+
+__global__ void __launch_bounds__ (256)
+bayer2rgb_half_kernel (HalfParams hp)
+{
+  __shared__ uint32_t tone[257];
+  const DeepParams &p = hp.d;
+  const bool has_tone = hp.colour && hp.s.has_tone;
+  if (has_tone) {               /* the colour kernel's rule: the whole workgroup copies, no wave leaves before the barrier */
+    constexpr size_t kToneOffset = offsetof (HalfParams, s) + offsetof (ColourStage, tone);
+    tone[threadIdx.x] = kernarg_table_entry<uint32_t> (kToneOffset, threadIdx.x);
+    if (threadIdx.x == 0)
+      tone[256] = kernarg_table_entry<uint32_t> (kToneOffset, 256);
+    __syncthreads ();
+  }
+  const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane ((int) (blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (wave >= p.nwaves)
+    return;
+  const int lane = (int) (threadIdx.x & 63u);
+  const uint32_t crow = fastdiv (wave, p.div_tiles_x);
+  const uint32_t tx = wave - crow * p.div_tiles_x.d;
+  const uint32_t frame = fastdiv (crow, p.div_chunks);
+  const int y0 = (int) (crow - frame * p.div_chunks.d) * kHalfRows;
+  const int y1 = y0 + kHalfRows < p.height ? y0 + kHalfRows : p.height;
+  const uint8_t *src = p.nlist
+      ? kernarg_table_entry<const uint8_t *> (offsetof (DeepParams, src_list), frame) : p.src + frame * p.src_frame_bytes;
+  uint8_t *dst = p.nlist
+      ? kernarg_table_entry<uint8_t *> (offsetof (DeepParams, dst_list), frame) : p.dst + frame * p.dst_frame_bytes;
+  const int g = (int) tx * 64 + lane;
+  const int left = p.width - kHalfLanePixels * g;       /* output pixels of the row from this lane on */
+  const int n = left < kHalfLanePixels ? left : kHalfLanePixels;
+  const int s = p.out_shift;
+  const int tshift = hp.out16 ? s : 8 - s;              /* 16 - depth */
+
+  /* raw[i] = source row 2 y0 + i; rows past the last quad row (a short last chunk) are never used and read that row.
+   * Sample width and "the row ends in this wave" are wave-uniform: a wave inside the row issues 2 kHalfRows plain wide
+   * loads back to back */
+  HalfRaw raw[2 * kHalfRows];
+  const bool wave_full = kHalfWavePixels * ((int) tx + 1) <= p.width;
+  const auto load_rows = [&] (auto full, bool in8) {
+#pragma unroll
+    for (int i = 0; i < 2 * kHalfRows; i++) {
+      const int r = 2 * y0 + i < 2 * p.height ? 2 * y0 + i : 2 * p.height - 1;
+      raw[i] = half_load<decltype (full)::value> (in8, src + (size_t) r * (size_t) p.src_stride, g, n);
+    }
+  };
+  if (wave_full && hp.in8)
+    load_rows (std::true_type (), true);
+  else if (wave_full)
+    load_rows (std::true_type (), false);
+  else if (hp.in8)
+    load_rows (std::false_type (), true);
+  else
+    load_rows (std::false_type (), false);
+#pragma unroll 1
+  for (int j = y0; j < y1; j++) {
+    uint32_t t[4], b[4];
+    half_pairs (hp, raw[0], t);
+    half_pairs (hp, raw[1], b);
+#pragma unroll
+    for (int i = 0; i + 2 < 2 * kHalfRows; i++)
+      raw[i] = raw[i + 2];
+    int v[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      /* green at the odd column of the top row (bggr, rggb), else the halves change places first */
+      const uint32_t tt = p.green_odd ? t[i] : __builtin_amdgcn_alignbit (t[i], t[i], 16);
+      const uint32_t bb = p.green_odd ? b[i] : __builtin_amdgcn_alignbit (b[i], b[i], 16);
+      const int c_top = (int) (tt & kLowHalves), c_bot = (int) (bb >> 16);
+      v[i][0] = p.red_odd ? c_bot : c_top;
+      v[i][1] = avg_i ((int) (tt >> 16), (int) (bb & kLowHalves));
+      v[i][2] = p.red_odd ? c_top : c_bot;
+    }
+    if (hp.colour) {            /* the colour kernel's stage: black level -> matrix -> clamp */
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int r = max (v[i][0] - hp.s.black[0], 0);
+        const int gr = max (v[i][1] - hp.s.black[1], 0);
+        const int bl = max (v[i][2] - hp.s.black[2], 0);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+          const int hi = __mul24 (hp.s.m_hi[3 * ch], r) + __mul24 (hp.s.m_hi[3 * ch + 1], gr)
+              + __mul24 (hp.s.m_hi[3 * ch + 2], bl);
+          const uint32_t lo = __umul24 ((uint32_t) hp.s.m_lo[3 * ch], (uint32_t) r)
+              + __umul24 ((uint32_t) hp.s.m_lo[3 * ch + 1], (uint32_t) gr)
+              + __umul24 ((uint32_t) hp.s.m_lo[3 * ch + 2], (uint32_t) bl);
+          v[i][ch] = min (max (hi + (int) ((lo + 2048u) >> 12), 0), p.vmax);
+        }
+      }
+    }
+    uint32_t x[4], y[4];        /* x = [R, G], y = [B, 0] at output depth: the MHC kernel's packing with C = R, D = B */
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      uint32_t o[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        if (has_tone) {
+          const uint32_t tv = (uint32_t) v[i][ch] << tshift;
+          const uint32_t ti = tv >> 8, tf = tv & 255u;
+          const uint32_t q = min ((__umul24 (tone[ti], 256u - tf) + __umul24 (tone[ti + 1], tf) + 128u) >> 8, 65535u);
+          o[ch] = hp.out16 ? q : q >> 8;
+        } else {
+          o[ch] = hp.out16 ? (uint32_t) v[i][ch] << s : (uint32_t) v[i][ch] >> s;
+        }
+      }
+      x[i] = o[0] | (o[1] << 16);
+      y[i] = o[2];
+    }
+    uint8_t *out = dst + (size_t) j * (size_t) p.dst_stride;
+    const uint32_t s0 = p.sel_cgd[0][0], s1 = p.sel_cgd[0][1];
+    if (hp.out16) {
+      u32x4 v0, v1;
+      emit_cgd<true> (x, y, s0, s1, v0, v1);
+      half_store16 (p, out, g, lane, v0, v1);
+    } else if (const int planes = p.planar) {
+      if (n > 0) {
+        const uint32_t col = 4u * (uint32_t) g;
+        half_plane (plane_row (p, out, planes & 3) + col, n, gather_byte<0> (x));
+        half_plane (plane_row (p, out, (planes >> 2) & 3) + col, n, gather_byte<2> (x));
+        half_plane (plane_row (p, out, (planes >> 4) & 3) + col, n, gather_byte<0> (y));
+      }
+    } else {
+      u32x4 vv, unused;
+      emit_cgd<false> (x, y, s0, s0, vv, unused);
+      half_store8 (out, g, n, p.px3 != 0, vv);
+    }
+  }
+}
+
+hipError_t launch_half (const DeepParams &p, bool in8, bool out16, const ColourStage *stage, int nframes,
+    hipStream_t stream)
+{
+  if (p.width < 1 || p.height < 1 || ((p.px3 || p.planar) && out16) || (p.px3 && p.planar))
+    return hipErrorInvalidValue;
+  const long long frames = p.nlist > 0 ? p.nlist : nframes;
+  if (p.nlist > kMaxList || frames <= 0)
+    return frames == 0 ? hipSuccess : hipErrorInvalidValue;
+  HalfParams q = {};
+  q.d = p;
+  q.d.groups = (p.width + kHalfLanePixels - 1) / kHalfLanePixels;
+  const int tiles_x = (q.d.groups + 63) / 64;
+  const long long chunks_per_frame = (p.height + kHalfRows - 1) / kHalfRows;
+  const long long waves = frames * chunks_per_frame * tiles_x;
+  if (frames * chunks_per_frame > 0x7fffffffLL || waves > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  q.d.div_tiles_x = make_fastdiv ((uint32_t) tiles_x);
+  q.d.div_chunks = make_fastdiv ((uint32_t) chunks_per_frame);
+  q.d.chunk0 = 0;
+  q.d.nwaves = (uint32_t) waves;
+  q.in8 = in8;
+  q.out16 = out16;
+  q.colour = stage != nullptr;
+  if (stage)
+    q.s = *stage;
+  hipLaunchKernelGGL (bayer2rgb_half_kernel, dim3 ((unsigned) ((waves + 3) / 4)), dim3 (256), 0, stream, q);
+  return hipGetLastError ();
+}
+
+/* ------------------------------------------------------------------------- */
 /* mosaic zone statistics                                                      */
 /* ------------------------------------------------------------------------- */
 /* Per zone and CFA site: sum and count of the samples in [lo, hi] and the number above hi (include/mibayer.h, group

@@ -116,7 +116,8 @@ enum
 #define DEFAULT_TIMEOUT_MS 10000
 #define DEFAULT_METHOD GST_MI_BAYER_METHOD_BILINEAR
 
-/* bayer2rgb's `method`: the reference's bilinear demosaic (bit-exact) or Malvar-He-Cutler (MIBAYER_FLAG_MHC) */
+/* bayer2rgb's `method`: the reference's bilinear demosaic (bit-exact), Malvar-He-Cutler (MIBAYER_FLAG_MHC) or one pixel
+ * per CFA quad (MIBAYER_FLAG_HALF) */
 static GType
 gst_mi_bayer_method_get_type (void)
 {
@@ -126,6 +127,8 @@ gst_mi_bayer_method_get_type (void)
         "bilinear"},
     {GST_MI_BAYER_METHOD_MHC,
         "Malvar-He-Cutler gradient-corrected 5x5 interpolation", "mhc"},
+    {GST_MI_BAYER_METHOD_HALF,
+        "Half size: one pixel per 2x2 CFA quad, nothing interpolated", "half"},
     {0, NULL, NULL}
   };
   if (g_once_init_enter (&type)) {
@@ -733,6 +736,7 @@ element_ensure_pool (GstMiBayerElement * self, gint video_stride)
       | (self->src_big_endian ? MIBAYER_FLAG_SRC_BIG_ENDIAN : 0)
       | (self->out16 ? MIBAYER_FLAG_DST_16BIT : 0)
       | (!inverse && self->act.method == GST_MI_BAYER_METHOD_MHC ? MIBAYER_FLAG_MHC : 0)
+      | (!inverse && self->act.method == GST_MI_BAYER_METHOD_HALF ? MIBAYER_FLAG_HALF : 0)
       | (want_colour ? MIBAYER_FLAG_COLOUR : 0);
   if (!element_parse_devices (self, &pc)) {
     element_defer_error (self, GST_LIBRARY_ERROR, GST_LIBRARY_ERROR_SETTINGS,
@@ -1066,9 +1070,93 @@ element_finalize (GObject * object)
 
 /* ---- caps (identical semantics to the reference) ------------------------------ */
 
+/* method=half: the raw side is width / 2 x height >> 1 of the bayer side.  One `width` or `height` value -- an int, a
+ * range, or a list of them -- of the one side as the value of the other:
+ *   towards raw    v -> v / 2; [a, b] -> [max (1, a / 2), b / 2]
+ *   towards bayer  width w -> 2 w, [a, b] -> [2 a, 2 b] in steps of 2; height h -> [2 h, 2 h + 1] (an odd last row is
+ *                  dropped), [a, b] -> [2 a, 2 b + 1]
+ * FALSE: nothing on the other side corresponds to it */
+static gboolean
+half_scale_value (const GValue * in, GValue * out, gboolean to_raw,
+    gboolean is_height)
+{
+  gint lo, hi;
+
+  if (GST_VALUE_HOLDS_LIST (in)) {
+    guint k, n = gst_value_list_get_size (in);
+
+    g_value_init (out, GST_TYPE_LIST);
+    for (k = 0; k < n; k++) {
+      GValue one = G_VALUE_INIT;
+
+      if (half_scale_value (gst_value_list_get_value (in, k), &one, to_raw,
+              is_height))
+        gst_value_list_append_and_take_value (out, &one);
+    }
+    if (gst_value_list_get_size (out) == 0) {
+      g_value_unset (out);
+      return FALSE;
+    }
+    return TRUE;
+  }
+  if (G_VALUE_HOLDS_INT (in)) {
+    lo = hi = g_value_get_int (in);
+  } else if (GST_VALUE_HOLDS_INT_RANGE (in)) {
+    lo = gst_value_get_int_range_min (in);
+    hi = gst_value_get_int_range_max (in);
+  } else {
+    return FALSE;
+  }
+  if (lo < 0 || hi < lo)
+    return FALSE;
+  if (to_raw) {
+    lo = MAX (1, lo / 2);
+    hi = hi / 2;
+  } else {
+    if (lo > G_MAXINT / 2)
+      return FALSE;
+    lo = 2 * lo;
+    hi = hi > (G_MAXINT - 1) / 2 ? (is_height ? G_MAXINT : G_MAXINT - 1)
+        : 2 * hi + (is_height ? 1 : 0);
+  }
+  if (hi < lo)
+    return FALSE;
+  if (lo == hi) {
+    g_value_init (out, G_TYPE_INT);
+    g_value_set_int (out, lo);
+  } else {
+    g_value_init (out, GST_TYPE_INT_RANGE);
+    if (!to_raw && !is_height)
+      gst_value_set_int_range_step (out, lo, hi, 2);
+    else
+      gst_value_set_int_range (out, lo, hi);
+  }
+  return TRUE;
+}
+
+/* ... both fields of a structure; FALSE: the structure has no counterpart */
+static gboolean
+half_scale_structure (GstStructure * s, gboolean to_raw)
+{
+  static const gchar *const fields[2] = { "width", "height" };
+  guint k;
+
+  for (k = 0; k < 2; k++) {
+    const GValue *in = gst_structure_get_value (s, fields[k]);
+    GValue out = G_VALUE_INIT;
+
+    if (in == NULL)
+      continue;
+    if (!half_scale_value (in, &out, to_raw, k == 1))
+      return FALSE;
+    gst_structure_take_value (s, fields[k], &out);
+  }
+  return TRUE;
+}
+
 /* reference gstbayer2rgb.c:289-322 and its mirror image gstrgb2bayer.c:128-159:
  * the bayer side and the raw side differ only in the media type name and in the
- * fields that describe the pixel encoding */
+ * fields that describe the pixel encoding -- and, with method=half, in size */
 static GstCaps *
 element_transform_caps (GstBaseTransform * base, GstPadDirection direction,
     GstCaps * caps, GstCaps * filter)
@@ -1077,10 +1165,18 @@ element_transform_caps (GstBaseTransform * base, GstPadDirection direction,
   const gboolean to_raw = (direction == GST_PAD_SINK) != IS_INVERSE (base);
   GstCaps *result = gst_caps_copy (caps);
   guint i, n = gst_caps_get_size (result);
+  const gboolean half = !IS_INVERSE (base)
+      && ELEMENT (base)->method == GST_MI_BAYER_METHOD_HALF;
 
   for (i = 0; i < n; i++) {
     GstStructure *s = gst_caps_get_structure (result, i);
 
+    if (half && !half_scale_structure (s, to_raw)) {
+      gst_caps_remove_structure (result, i);
+      i--;
+      n--;
+      continue;
+    }
     if (to_raw) {
       gst_structure_set_name (s, "video/x-raw");
       gst_structure_remove_field (s, "format");
@@ -1228,6 +1324,15 @@ element_set_caps (GstBaseTransform * base, GstCaps * incaps, GstCaps * outcaps)
   self->out16 = GST_VIDEO_INFO_FORMAT (&info) == GST_VIDEO_FORMAT_ARGB64;
   if (inverse && self->out16)
     return FALSE;
+  /* method=half: one output pixel per CFA quad, anything else is not-negotiated */
+  if (!inverse && self->method == GST_MI_BAYER_METHOD_HALF
+      && (GST_VIDEO_INFO_WIDTH (&info) != self->width / 2
+          || GST_VIDEO_INFO_HEIGHT (&info) != self->height >> 1)) {
+    EL_WARNING (self, "refusing %dx%d -> %dx%d: method=half converts to %dx%d",
+        self->width, self->height, GST_VIDEO_INFO_WIDTH (&info),
+        GST_VIDEO_INFO_HEIGHT (&info), self->width / 2, self->height >> 1);
+    return FALSE;
+  }
   self->r_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 0) / (self->out16 ? 2 : 1);
   self->g_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 1) / (self->out16 ? 2 : 1);
   self->b_off = GST_VIDEO_INFO_COMP_OFFSET (&info, 2) / (self->out16 ? 2 : 1);
@@ -1700,7 +1805,9 @@ gst_mi_bayer_element_class_setup (GstMiBayerElementClass * klass,
             "bilinear: the stock element's algorithm, bit-exact; mhc: "
             "Malvar-He-Cutler gradient-corrected interpolation (fewer zipper "
             "and colour-fringe artefacts on edges, not bit-exact with the "
-            "stock element)", gst_mi_bayer_method_get_type (), DEFAULT_METHOD,
+            "stock element); half: one output pixel per 2x2 CFA quad from the "
+            "quad's own samples, the output is width/2 x height/2 (an odd last "
+            "row is dropped)", gst_mi_bayer_method_get_type (), DEFAULT_METHOD,
             G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY |
             G_PARAM_STATIC_STRINGS));
   if (!inverse)

@@ -23,7 +23,8 @@ G_BEGIN_DECLS
 typedef enum
 {
   GST_MI_BAYER_METHOD_BILINEAR = 0,     /* the reference's algorithm, bit-exact */
-  GST_MI_BAYER_METHOD_MHC = 1           /* Malvar-He-Cutler (MIBAYER_FLAG_MHC) */
+  GST_MI_BAYER_METHOD_MHC = 1,          /* Malvar-He-Cutler (MIBAYER_FLAG_MHC) */
+  GST_MI_BAYER_METHOD_HALF = 2          /* one pixel per CFA quad (MIBAYER_FLAG_HALF): the output is half the size */
 } GstMiBayerMethod;
 
 typedef struct _GstMiBayerElement GstMiBayerElement;

@@ -79,6 +79,8 @@ extern "C" {
 /* 5, later additive: noise reduction -- struct mibayer_nr and the entry points of group `nr`; a context with the curve
  * off converts what it converted. */
 /* 5, later additive: mosaic focus statistics -- struct mibayer_focus_zone and the entry points of group `focus`. */
+/* 5, later additive: half-size demosaic -- MIBAYER_FLAG_HALF, a flag only; no struct field and no entry point was
+ * added, and a cfg without the flag means what it meant. */
 #define MIBAYER_ABI_VERSION 5
 
 /* MIBAYER ABI GROUPS -- which of the entry points are the drop-in and which are not.  The ABI is
@@ -374,6 +376,36 @@ int mibayer_pool_set_colour (mibayer_pool *pool, const mibayer_colour *colour);
 int mibayer_colour_matrix (const double gains[3], const double ccm[9], int32_t out[9]);
 /* tone[i] = round (65536 f (i / 256)) for MIBAYER_TONE_*; `gamma` is read by MIBAYER_TONE_GAMMA only */
 int mibayer_colour_tone (int curve, double gamma, uint32_t tone[257]);
+
+/* ---- half-size demosaic (additive within version 5: a flag only) -------------------------------------------------- */
+
+/* One RGB pixel per CFA quad (dcraw -h, LibRaw half_size): a quarter of the pixels, each built from the four samples of
+ * its own quad only -- nothing interpolated, no neighbourhood, no border rule.  What previews, analytics and tensor
+ * ingest take, without a full demosaic and a scaler behind it.
+ *   geometry  cfg.width / cfg.height stay the MOSAIC's (W, H) under the usual rules: even W >= 4, H >= 3, W <= 2^26.
+ *             The output is OW = W / 2 by OH = H >> 1 pixels; the last row of an odd height has no quad and is dropped.
+ *             OW may be odd (W = 6 -> 3).
+ *   samples   S, masking, byte order and depth exactly as in group `stats`.  Output pixel (X, Y) reads S (2X + dx,
+ *             2Y + dy), dx, dy in {0, 1}: R = the quad's red sample, B = its blue one, G = (Ga + Gb + 1) >> 1 of its
+ *             two green samples at native depth; the Bayer order says which is which.  The pixel sits at the quad's
+ *             CENTRE: R and B are each half an output pixel (one sample) off it, in opposite directions.
+ *   output    from (R, G, B) on everything is the deep path's: v >> (bits - 8) for 8-bit channels, v << (16 - bits) for
+ *             16-bit ones, alpha, the four 4-byte layouts, MIBAYER_FLAG_DST_16BIT / _DST_BIG_ENDIAN, _DST_24BIT and
+ *             _DST_PLANAR; with MIBAYER_FLAG_COLOUR steps 1-4 of the stage run verbatim on (R, G, B).
+ *   strides   dst_stride default ROUND_UP_4 (px * OW), px = the bytes of a pixel in a row (4 / 8 / 3 / 1); >= px * OW and
+ *             a multiple of 4 (8 for 16-bit channels), else MIBAYER_ERR_GEOMETRY.  Only the first px * OW bytes of a
+ *             row are written.  src_stride as without the flag.
+ *   sizes     a frame is dst_stride * OH bytes, x 3 when planar (plane k at dst + k * dst_stride * OH): what a batch's
+ *             dst_frame_bytes must at least be, where d_dsts[f] points and what the host path's `dst` holds.
+ * With MIBAYER_FLAG_MHC (there is nothing to interpolate), MIBAYER_FLAG_RGB2BAYER or variant != 0 it is MIBAYER_ERR_ARG;
+ * MIBAYER_FLAG_HIPGRAPH is accepted and the host path runs without graphs.  A HALF context has one kernel shape and no
+ * plans, like a deep context: mibayer_autotune[_list], mibayer_set_plan[_for], mibayer_plan_selectors and
+ * mibayer_launch_geometry return MIBAYER_ERR_ARG; mibayer_fill_synthetic works when the mosaic is 8-bit;
+ * mibayer_ctx_variant_name names the half-size kernel.  The host path launches each frame whole (no bands).  Groups
+ * `stats`, `hist`, `focus`, `shading`, `dpc` and `nr` work on the mosaic and are unchanged: grids, windows and limits in
+ * source coordinates, and on the host path they run before the half-size launch as before the full one.
+ * (Bit 23: bits 17, 18, 20, 24 and 31 stay unknown flags.) */
+#define MIBAYER_FLAG_HALF (1u << 23)
 
 /* ---- mosaic zone statistics (additive within version 5: a struct and the entry points of group `stats`) -------- */
 
